@@ -2,6 +2,7 @@
 """Benchmark of the per-video inference hot path on MI355X (contract: the round prompt / DESIGN.md section 6).
 
     python bench.py --gpus N --steps K --warmup W         (N > 1 spawns its own ranks when WORLD_SIZE is unset)
+    python bench.py ... --dump-outputs DIR                (also writes the last timed step's results to DIR/*.npy)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -85,7 +86,13 @@ def parse():
     ap.add_argument("--no-train", action="store_true", help="skip the test-time-training leg (BASELINE config 5; extra key `train`)")
     ap.add_argument("--train-widths", default="384", help="feature widths of the training leg, comma-separated (384 = north star, 1024 = the reference's own)")
     ap.add_argument("--train-iters", type=int, default=30, help="timed iterations of the training leg per width and mode")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step returned (trajectories and occlusion flags per video) to DIR/<name>.npy "
+                         "in float32; above 64 MB a fixed, seeded sample of query rows is kept")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def self_launch(args) -> int:
@@ -132,6 +139,43 @@ def train_leg(args):
         except Exception as ex:  # noqa: BLE001
             res[f"C={width}"] = {"error": f"{type(ex).__name__}: {str(ex)[:200]}"}
     return res
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, res):
+    """--dump-outputs: the arrays the last timed step handed its caller -- trajectories [N, T, 2] and occlusion flags [N, T]
+    of every video -- as float32 .npy files.  Above DUMP_BUDGET_BYTES the same seeded sample of query rows is kept in every file."""
+    import numpy as np
+    if isinstance(res, dict):        # run_sharded / run_scheduled on rank 0: {video: (traj, occ)}
+        items = [(f"_v{v:03d}", res[v]) for v in sorted(res)]
+    elif isinstance(res, list):      # one video per rank, gathered on rank 0
+        items = [(f"_r{r}", x) for r, x in enumerate(res)]
+    else:
+        items = [("", res)]
+    arrays = {}
+    for suffix, pair in items:
+        if pair is None or pair[0] is None:
+            continue
+        arrays["traj" + suffix] = pair[0].detach().to(torch.float32).cpu()
+        arrays["occ" + suffix] = pair[1].detach().to(torch.float32).cpu()
+    if not arrays:
+        raise SystemExit("--dump-outputs: the timed step returned no outputs ('track' must be one of --stages)")
+    total = sum(a.numel() * 4 for a in arrays.values())
+    n = min(a.shape[0] for a in arrays.values())
+    rows = None
+    budget = DUMP_BUDGET_BYTES - 1024 * len(arrays)    # (room for the .npy headers)
+    if total > budget:
+        keep = max(1, n * budget // total)
+        rows = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:keep].sort().values
+        arrays = {k: a[rows] for k, a in arrays.items()}
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, f"{k}.npy"), a.numpy())
+    return {"dir": dirname, "files": sorted(f"{k}.npy" for k in arrays), "dtype": "float32",
+            "bytes": sum(a.numel() * 4 for a in arrays.values()),
+            "query_rows": "all" if rows is None else f"{len(rows)} of {n}, seeded sample (torch.randperm, seed 0)"}
 
 
 def main():
@@ -286,9 +330,12 @@ def main():
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = step()
     barrier()
     dt = time.perf_counter() - t0
+    # copied off the device before any later pass can reuse the buffers
+    dumped = dump_outputs(args.dump_outputs, last) if args.dump_outputs and rank == 0 else None
+    del last
     # shader clock / board power of whole steps: sampled over a REPEAT of the steps after the timed region (the polling thread
     # shares the interpreter with the launch loop; the timed region stays untouched)
     sampler = clock_power = None
@@ -716,6 +763,7 @@ def main():
                        "parallelism": (f"query-parallel x{world} (frames split for P1/P2, queries for P3)" if qpar
                                        else f"video-parallel x{world}")},
             "videos30": videos30, "per_rank": per_rank, "roofline": roofline, "clock_power": clock_power, "cpu_baseline": cpu, "parity_sample": parity,
+            "dump_outputs": dumped,
         }
         if world == 1 and not args.no_train:
             out["train"] = train_leg(args)

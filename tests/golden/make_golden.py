@@ -258,6 +258,13 @@ if __name__ == "__main__":
         np.savez_compressed(path, **res)
         print("ref_scripts_synth", {k: v.shape for k, v in res.items()},
               dict(zip(res["cfg3_metric_names"], res["cfg3_metric_values"])), os.path.getsize(path) // 1024, "KiB")
+    if "ref_units" in names:
+        names.remove("ref_units")
+        import ref_units
+        res = ref_units.reference_values(ref_harness.load(), tempfile.mkdtemp())
+        path = os.path.join(OUT, ref_units.GOLDEN)
+        np.savez_compressed(path, **res)
+        print("ref_units", len(res), "arrays", os.path.getsize(path) // 1024, "KiB")
     if "p1_small" in names:
         names.remove("p1_small")
         res = run_reference_p1()

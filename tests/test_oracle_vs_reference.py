@@ -1,51 +1,38 @@
-"""CPU, build container only: oracle restatements vs the live UN-MODIFIED reference modules (skipped where
-/root/reference is absent, e.g. on the GPU box)."""
+"""CPU: oracle restatements vs the UN-MODIFIED reference modules, through the reference's outputs on seeded inputs stored in
+tests/golden/ref_units.npz (tests/golden/ref_units.py builds the inputs and, under make_golden.py, runs the reference)."""
+import os
+
+import numpy as np
 import pytest
 import torch
 
+import ref_units as U
 from oracle import ref_algo as A
-from oracle import ref_harness
 
-pytestmark = pytest.mark.skipif(not ref_harness.available(), reason="/root/reference not present")
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", U.GOLDEN)
 
 
-def test_delta_dino_and_align_match_reference():
-    from dino_tracker_amd import synth
-    R = ref_harness.load()
-    c = 24
-    sd = synth.synth_delta_dino_weights(c, seed=7)
-    net = R.delta_dino.DeltaDINO(channels=[3, 64, 128, 256, c], vit_stride=7).eval()
-    net.load_state_dict(sd)
-    frames = synth.synth_video(2, 98, 126, seed=5)
-    vit = torch.zeros(2, c, 13, 17)
-    with torch.no_grad():
-        ref = net(frames, vit)
+@pytest.fixture(scope="module")
+def gold():
+    with np.load(GOLD) as z:
+        return {k: z[k] for k in z.files}
+
+
+def test_delta_dino_and_align_match_reference(gold):
+    c, sd, frames, vit = U.delta_dino_case()
+    ref = torch.from_numpy(gold["delta_dino"])
+    assert ref.shape == (2, c, 13, 17)
     cnn = A.delta_dino_cnn(frames, sd)
     assert cnn.shape[-2:] == (13, 16)  # 98->49->25->13, 126->63->32->16
     out = A.align_to_vit_grid(cnn, 13, 17)
     assert (out - ref).abs().max() < 1e-6
 
 
-def test_tracker_forward_matches_reference():
-    import os
-    import tempfile
-    from dino_tracker_amd import synth
-    R = ref_harness.load()
-    H, W, T, C = 112, 154, 5, 16
-    ph, pw = A.feature_grid(H, W)
-    video = synth.synth_video(T, H, W, seed=21)
-    feats = synth.synth_features(T, C, ph, pw, seed=22)
-    head = synth.synth_head_weights(23)
-    tmp = tempfile.mkdtemp()
-    torch.save(feats, os.path.join(tmp, "e.pt"))
-    trk = R.tracker.Tracker(video=video, ckpt_path=tmp, dino_embed_path=os.path.join(tmp, "e.pt"), device="cpu")
-    trk.tracker_head.load_state_dict(head)
-    pts = torch.tensor([[30.0, 40.0, 1.0], [100.5, 77.25, 3.0], [2.0, 3.0, 0.0], [150.0, 110.0, 4.0]])
-    fs = torch.arange(T).int()
-    with torch.no_grad():
-        ref = trk((pts, pts[:, 2].long(), torch.tensor([4, 0, 2, 2]), fs), use_raw_features=True)
+def test_tracker_forward_matches_reference(gold):
+    H, W, T, video, feats, head, pts, tgt = U.tracker_forward_case()
+    ref = torch.from_numpy(gold["tracker_forward"])
     src = A.sample_bilinear(feats, pts[:, :2], pts[:, 2], H, W)
-    mine = A.track(src, feats, torch.tensor([4, 0, 2, 2]), head, H, W)
+    mine = A.track(src, feats, tgt, head, H, W)
     refpx = torch.stack([(ref[:, 0] + 1) / 2 * (W - 1), (ref[:, 1] + 1) / 2 * (H - 1)], 1)
     assert (mine - refpx).abs().max() < 1e-3
 
@@ -62,28 +49,11 @@ def test_vit_blocks_match_hf_port():
     assert r.returncode == 0, r.stdout + r.stderr
 
 
-def test_tapvid_metrics_match_reference(tmp_path):
+def test_tapvid_metrics_match_reference(gold):
     """oracle.tapvid_metrics vs the reference's compute_tapvid_metrics_for_video (eval/metrics.py:150-223) fed through
     its own .npy / pickle-dict interface, on random tracks with realistic error scales."""
-    import numpy as np
-    ref_harness.load()
-    import eval.metrics as EM
-    g = np.random.default_rng(0)
-    T = 9
-    cfg = {"video_idx": 3, "h": 256, "w": 256, "query_points": {}, "target_points": {}, "occluded": {}}
-    preds = {}
-    for f, n in ((0, 5), (4, 7), (8, 3)):
-        gt = g.uniform(0, 255, (n, T, 2)).astype(np.float32)
-        occ = g.uniform(size=(n, T)) < 0.3
-        noise = g.normal(size=(n, T, 2)) * g.choice([0.3, 1.5, 6.0, 30.0], size=(n, T, 1))
-        pred = ((gt + noise) * np.array([854 / 256, 476 / 256])).astype(np.float32)  # predictions live at 854 x 476
-        pocc = occ ^ (g.uniform(size=(n, T)) < 0.2)
-        cfg["query_points"][f] = gt[:, f].tolist()
-        cfg["target_points"][f], cfg["occluded"][f] = gt, occ
-        preds[f] = (pred, pocc)
-        np.save(tmp_path / f"trajectories_{f}.npy", pred)
-        np.save(tmp_path / f"occlusion_preds_{f}.npy", pocc)
-    want = EM.compute_tapvid_metrics_for_video(str(tmp_path), str(tmp_path), {"videos": [cfg]}, 3, pred_video_sizes=[854, 476])
+    cfg, preds = U.tapvid_case()
+    want = dict(zip(gold["tapvid_names"].tolist(), gold["tapvid_values"].tolist()))
     frames = list(cfg["query_points"])
     got = A.tapvid_metrics(np.concatenate([[f] * len(cfg["query_points"][f]) for f in frames]),
                            np.concatenate([cfg["occluded"][f] for f in frames]),
@@ -96,18 +66,12 @@ def test_tapvid_metrics_match_reference(tmp_path):
     assert 0.05 < want["average_jaccard"] < 0.95  # a non-degenerate case
 
 
-def test_best_buddies_match_reference(tmp_path):
+def test_best_buddies_match_reference(gold):
     """oracle.best_buddies_pair vs the reference script preprocessing_dino_bb/extract_dino_best_buddies.py run as is (CPU)."""
-    import types
-    from dino_tracker_amd import synth
-    ref_harness.load()
-    import preprocessing_dino_bb.extract_dino_best_buddies as BB
-    T, C, Hh, Ww = 3, 16, 98, 126
-    feats = synth.synth_features(T, C, 13, 17, seed=33)
-    torch.save(feats, tmp_path / "emb.pt")
-    out = tmp_path / "bb" / "bb.pt"
-    BB.run(types.SimpleNamespace(dino_emb_path=str(tmp_path / "emb.pt"), h=Hh, w=Ww, stride=7, out_path=str(out)))
-    bb = torch.load(out)
+    T, Hh, Ww, feats = U.best_buddies_case()
+    C = feats.shape[1]
+    bb = {k: {f: torch.from_numpy(gold[f"bb_{k}_{f}"]) for f in ("source_coords", "target_coords", "cos_sims")}
+          for k in gold["bb_pairs"].tolist()}
     from dino_tracker_amd.best_buddies import create_meshgrid
     coords = create_meshgrid(Hh, Ww)
     tm = feats.permute(0, 2, 3, 1).reshape(T, -1, C)
@@ -122,49 +86,34 @@ def test_best_buddies_match_reference(tmp_path):
             assert (e["cos_sims"].cpu() - cs).abs().max() < 1e-6
 
 
-def test_bb_nms_ratio_matches_reference_functions(tmp_path):
+def test_bb_nms_ratio_matches_reference_functions(gold):
     """N4 second half: oracle.bb_nms_ratio (no NMS sweep: arg-max + best non-overlapping candidate) vs the reference's
     get_bb_sim_indices / compute_bb_nms / compute_max_r (preprocessing_dino_bb/compute_dino_bb_nms.py:12-78) run as they
     are, around the restated torchvision.ops.batched_nms of oracle/shims (torchvision is absent: that one op is
     'parity unpinned').  Smooth random feature fields give rows with several separated peaks, so r takes values over (0, 1)."""
-    from dino_tracker_amd import synth
-    ref_harness.load()
-    import preprocessing_dino_bb.compute_dino_bb_nms as NMS
-    from dino_tracker_amd.best_buddies import create_meshgrid
-    T, C, Hh, Ww = 3, 32, 238, 322     # 33 x 45 = 1485 cells >= topk
-    ph, pw = 33, 45
-    feats = synth.synth_features(T, C, ph, pw, seed=35)
-    coords = create_meshgrid(Hh, Ww)
-    tm = feats.permute(0, 2, 3, 1).reshape(T, -1, C)
-    bbs = {}
-    for s in range(T):
-        for t in range(T):
-            if s != t:
-                si, ti, cs = A.best_buddies_pair(tm[s], tm[t])
-                bbs[f"{s}_{t}"] = {"source_coords": coords[si], "target_coords": coords[ti], "cos_sims": cs}
+    T, ph, pw, feats, coords, tm, bbs = U.bb_nms_case()
     seen_r = []
-    for (s, t) in ((0, 1), (0, 2), (1, 2)):
-        want, got = {}, {}
+    for (s, t) in U.BB_NMS_PAIRS:
+        got = {}
         for a, b in ((s, t), (t, s)):
-            e = {k: v.clone() for k, v in bbs[f"{a}_{b}"].items()}
-            want[(a, b)] = NMS.compute_bb_nms(e, a, b, feats, coords, 7, 50, 0.2)
+            e = bbs[f"{a}_{b}"]
             src = tm[a][(e["source_coords"][:, 1].long() - 7) // 7 * pw + (e["source_coords"][:, 0].long() - 7) // 7]
             aff = (src @ tm[b].t()) / torch.clamp(src.norm(dim=1)[:, None] * tm[b].norm(dim=1)[None], min=1e-8)
             top2, r = A.bb_nms_ratio(aff, pw, 50.0, 0.2, 400)
             got[(a, b)] = (top2, r)
-            assert (want[(a, b)]["peak_affs"] - top2).abs().max() < 1e-6
-            assert (want[(a, b)]["r"] - r).abs().max() < 1e-6
+            assert (torch.from_numpy(gold[f"nms_{a}_{b}_peak_affs"]) - top2).abs().max() < 1e-6
+            assert (torch.from_numpy(gold[f"nms_{a}_{b}_r"]) - r).abs().max() < 1e-6
             seen_r.append(r)
-        bb, bbr = NMS.compute_max_r(want[(s, t)], want[(t, s)])
+        bb_r, bbr_r = torch.from_numpy(gold[f"max_r_{s}_{t}"]), torch.from_numpy(gold[f"max_r_{t}_{s}"])
         # compute_max_r by index arithmetic: pair i of (s, t) <-> the pair of (t, s) whose source is i's target
         cell = lambda xy: (xy[:, 1].long() - 7) // 7 * pw + (xy[:, 0].long() - 7) // 7  # noqa: E731
         where = torch.full((ph * pw,), -1, dtype=torch.long)
         where[cell(bbs[f"{t}_{s}"]["source_coords"])] = torch.arange(bbs[f"{t}_{s}"]["source_coords"].shape[0])
         j = where[cell(bbs[f"{s}_{t}"]["target_coords"])]
         m = torch.maximum(got[(s, t)][1], got[(t, s)][1][j])
-        assert (bb["r"] - m).abs().max() < 1e-6
+        assert (bb_r - m).abs().max() < 1e-6
         rr = got[(t, s)][1].clone()
         rr[j] = m
-        assert (bbr["r"] - rr).abs().max() < 1e-6
+        assert (bbr_r - rr).abs().max() < 1e-6
     allr = torch.cat(seen_r)
     assert allr.numel() > 50 and (allr > 0.05).float().mean() > 0.3 and (allr < 0.9).float().mean() > 0.3  # non-degenerate

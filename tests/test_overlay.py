@@ -115,8 +115,11 @@ def test_run_videos_partitions_data_paths_over_ranks(tmp_path):
         d.mkdir()
         paths.append(str(d))
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    # a launch on a node without a device restriction of its own (a restricted one: the next test); the caller's
+    # HIP_VISIBLE_DEVICES / CUDA_VISIBLE_DEVICES would otherwise decide which GPU each rank may address
+    base = {k: v for k, v in os.environ.items() if k not in ("HIP_VISIBLE_DEVICES", "CUDA_VISIBLE_DEVICES")}
     for rank in range(3):
-        env = dict(os.environ, PYTHONPATH=root, RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE="3")
+        env = dict(base, PYTHONPATH=root, RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE="3")
         r = subprocess.run([sys.executable, "-m", "dino_tracker_amd.run_videos", str(script), "--data-paths"] + paths +
                            ["--", "--config", "c.yaml"], env=env, capture_output=True, text=True, cwd=str(tmp_path))
         assert r.returncode == 0, r.stderr[-2000:]
@@ -127,7 +130,7 @@ def test_run_videos_partitions_data_paths_over_ranks(tmp_path):
     bad = tmp_path / "bad.py"
     bad.write_text("import sys\nsys.exit(3 if 'video1' in sys.argv[2] else 0)\n")
     r = subprocess.run([sys.executable, "-m", "dino_tracker_amd.run_videos", str(bad), "--data-paths"] + paths[:3],
-                       env=dict(os.environ, PYTHONPATH=root), capture_output=True, text=True, cwd=str(tmp_path))
+                       env=dict(base, PYTHONPATH=root), capture_output=True, text=True, cwd=str(tmp_path))
     assert r.returncode == 1 and "video1" in r.stderr
 
 

@@ -1,18 +1,28 @@
 """N1 (test-time training), CPU: the differentiable statement of the path (dino_tracker_amd/train_ops.py) and the
-trajectory samplers against the UN-MODIFIED reference modules imported from /root/reference -- values, gradients with
-respect to every parameter and input, BatchNorm running statistics, and seeded sampler draws.  Skipped where the reference
-is absent (the GPU box); tests/test_gpu_train.py covers the device there against committed goldens."""
+trajectory samplers against the UN-MODIFIED reference modules -- values, gradients with respect to every parameter and input,
+BatchNorm running statistics, and seeded sampler draws.  The alignment, config and sampler comparisons read the reference's
+outputs from tests/golden/ref_units.npz (make_golden.py); the tests that run the reference's modules themselves are skipped
+where it is absent; tests/test_gpu_train.py covers the device against committed goldens."""
 import os
 import re
 import sys
 
+import numpy as np
 import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import ref_units as U  # noqa: E402
 from oracle import ref_harness  # noqa: E402
 
-pytestmark = pytest.mark.skipif(not ref_harness.available(), reason="reference not present")
+needs_ref = pytest.mark.skipif(not ref_harness.available(), reason="reference not present")
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", U.GOLDEN)
+
+
+@pytest.fixture(scope="module")
+def gold():
+    with np.load(GOLD) as z:
+        return {k: z[k] for k in z.files if k.startswith("train_")}
 
 from dino_tracker_amd import train_ops  # noqa: E402
 from dino_tracker_amd.dataset import DinoTrackerSampler, RangeNormalizer  # noqa: E402
@@ -31,6 +41,7 @@ def _randomise(module, seed):
                 b.copy_(torch.rand(b.shape, generator=g) + 0.5)
 
 
+@needs_ref
 def test_delta_dino_train_mode_matches_reference():
     """Forward value, gradients of all 16 parameter tensors and of the input, running statistics after two steps.  The
     gradient of this chain (four conv + batch-statistics BatchNorm + ReLU stages) is ill-conditioned in float32 -- two
@@ -82,16 +93,14 @@ def test_delta_dino_train_mode_matches_reference():
             assert torch.allclose(sd_t[k].float(), sd_o[k].float(), rtol=1e-5, atol=1e-6), k
 
 
-def test_align_matrices_equal_grid_sample():
-    ref = ref_harness.load()
-    g = torch.Generator().manual_seed(2)
-    for (hc, wc, h, w) in ((60, 107, 67, 121), (9, 13, 9, 13), (16, 107, 17, 121)):
-        cnn = torch.randn(2, 5, hc, wc, generator=g)
-        want = ref.models_utils.align_cnn_vit_features(torch.zeros(2, 5, h, w), cnn, cnn_stride=8, vit_stride=7)
+def test_align_matrices_equal_grid_sample(gold):
+    for i, (cnn, h, w) in enumerate(U.align_cases()):
+        want = torch.from_numpy(gold[f"train_align_{i}"])    # models/utils.py align_cnn_vit_features of the reference
         got = train_ops.align_cnn_to_vit(cnn, h, w, 7, 14, 8)
         assert (got - want).abs().max() < 5e-6
 
 
+@needs_ref
 def test_sampling_correlation_head_match_reference_with_gradients():
     """Tracker.get_point_predictions (tracker.py:171-180) of the reference, assembled from its own methods, against
     train_ops: predictions and gradients with respect to the frame embeddings and the four head tensors -- including maps
@@ -165,24 +174,11 @@ def test_sampling_correlation_head_match_reference_with_gradients():
         assert ((p * (d <= 35)).sum(dim=(1, 2)) < 1e-8).any()
 
 
-def test_samplers_draw_what_the_reference_draws():
-    ref = ref_harness.load()
-    g = torch.Generator().manual_seed(4)
-    T, W, H = 12, 210, 126
-
-    def trajectories(n):
-        tr = torch.rand(n, T, 2, generator=g) * torch.tensor([W - 1.0, H - 1.0])
-        tr[torch.rand(n, T, generator=g) < 0.45] = float("nan")
-        return tr
-    fg, bg = trajectories(300), trajectories(500)
-    rn_t = ref.dataset.RangeNormalizer(shapes=(W, H, T))
-    rn_o = RangeNormalizer(shapes=(W, H, T))
-    kw = dict(batch_size=64, dst_range=(-1, 1), fg_traj_ratio=0.5, num_frames=4, keep_in_cpu=False)
-    theirs = ref.dataset.DinoTrackerSampler(range_normalizer=rn_t, fg_trajectories=fg.clone(), bg_trajectories=bg.clone(), **kw)
-    ours = DinoTrackerSampler(range_normalizer=rn_o, fg_trajectories=fg.clone(), bg_trajectories=bg.clone(), **kw)
-    for seed in range(5):
-        torch.manual_seed(seed)
-        a = theirs()
+def test_samplers_draw_what_the_reference_draws(gold):
+    T, W, H, fg, bg, kw = U.sampler_case()
+    ours = DinoTrackerSampler(range_normalizer=RangeNormalizer(shapes=(W, H, T)), fg_trajectories=fg.clone(), bg_trajectories=bg.clone(), **kw)
+    for seed in U.SAMPLER_SEEDS:
+        a = {k: torch.from_numpy(gold[f"train_sampler_{seed}_{k}"]) for k in gold[f"train_sampler_{seed}_keys"].tolist()}
         torch.manual_seed(seed)
         b = ours()
         assert a.keys() == b.keys()
@@ -193,15 +189,15 @@ def test_samplers_draw_what_the_reference_draws():
         assert not torch.isnan(b["t1_points"]).any() and not torch.isnan(b["t2_points_normalized"]).any()
 
 
-def test_restated_train_yaml_matches_reference():
-    """tests/golden/train_data.TRAIN_YAML (what the reference-free data directory is configured from) == config/train.yaml."""
-    import yaml
+def test_restated_train_yaml_matches_reference(gold):
+    """tests/golden/train_data.TRAIN_YAML (what the reference-free data directory is configured from) == config/train.yaml
+    (compared through the digest of the parsed document)."""
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
     import train_data as TD
-    with open(os.path.join(ref_harness.REFERENCE_ROOT, "config", "train.yaml")) as fh:
-        assert yaml.safe_load(fh.read()) == TD.TRAIN_YAML
+    assert U.yaml_digest(TD.TRAIN_YAML) == str(gold["train_yaml_sha256"])
 
 
+@needs_ref
 @pytest.mark.skipif(not os.environ.get("DTK_SLOW_CPU_TESTS"), reason="~4 min of reference training on CPU: set DTK_SLOW_CPU_TESTS=1 "
                     "(measured in round 4: all 21 losses within 2.6e-6 of tests/golden/ref_train_synth.npz)")
 def test_train_twin_pinned_against_reference_on_cpu(tmp_path):

@@ -1,104 +1,45 @@
 """N1, CPU: the loss terms of dino_tracker_amd/trainer.py against the UN-MODIFIED methods of the reference's trainer
-(dino_tracker.py:128-352) -- the reference methods run with torch's random functions recorded, the recorded draws are
-turned into the explicit selections the device-side terms take, and values and gradients must agree.  Plus the properties
-of the key-based subset sampling and of the device-side batch sampler.  Skipped where the reference is absent."""
+(dino_tracker.py:128-352) -- the reference methods ran with torch's random functions recorded (tests/golden/ref_units.py,
+stored in tests/golden/ref_units.npz by make_golden.py), the recorded draws are turned into the explicit selections the
+device-side terms take, and values and gradients must agree.  Plus the properties of the key-based subset sampling and of the
+device-side batch sampler."""
 import os
 import sys
 import types
 
+import numpy as np
 import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from oracle import ref_harness  # noqa: E402
-
-pytestmark = pytest.mark.skipif(not ref_harness.available(), reason="reference not present")
-
+import ref_units as U  # noqa: E402
 from dino_tracker_amd import trainer as T  # noqa: E402
 from dino_tracker_amd.dataset import DinoTrackerSampler, RangeNormalizer  # noqa: E402
 
-CONFIG = {
-    "cl_n_frames": 4, "cl_points_per_pair": 40, "cl_fg_points_ratio": 0.7, "cl_temp": 0.1, "cl_div_dino_bb": 700,
-    "cl_div_ref_bb": 900, "bb_amb_sig_a": 27, "bb_amb_sig_b": -5.7, "dino_patch_size": 14, "cyc_gamma": 0.8,
-    "lambda_cyc": 0.5, "lambda_cl_ref_bb": 5e-5, "lambda_cl_dino_bb": 2.5e-4, "lambda_emb_norm": 1e-4, "lambda_angle": 1e-4,
-}
-H, W, FRAMES, C = 126, 182, 6, 16
+CONFIG = U.TRAINER_CONFIG
+H, W, FRAMES, C = U.TRAINER_H, U.TRAINER_W, U.TRAINER_FRAMES, U.TRAINER_C
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", U.GOLDEN)
+
+
+@pytest.fixture(scope="module")
+def gold():
+    with np.load(GOLD) as z:
+        return {k: z[k] for k in z.files if k.startswith("trainer_")}
 
 
 @pytest.fixture()
-def world(monkeypatch):
-    """The reference trainer module, an instance of its class and of the derived class (no __init__: attributes set by
-    hand), a synthetic scene: masks, best buddies of every frame pair, a stand-in model holding the batch's embeddings."""
-    ref = ref_harness.load()
-    monkeypatch.setattr(torch.Tensor, "cuda", lambda self, *a, **k: self)
-    import models.utils as mu
-    monkeypatch.setattr(mu.get_vit_feature_coords_from_mask, "__defaults__", (7, 14, "cpu"))
-    import dino_tracker as ref_dt
-    assert ref_harness.REFERENCE_ROOT in ref_dt.__file__
-    g = torch.Generator().manual_seed(0)
-    h, w = (H - 14) // 7 + 1, (W - 14) // 7 + 1
-    fg_masks = torch.zeros(FRAMES, H, W)
-    for f in range(FRAMES):
-        fg_masks[f, 20 + 3 * f:90, 30:120 + 5 * f] = 1.0
-    pairs = {}
-    for s in range(FRAMES):
-        for t in range(FRAMES):
-            if s == t:
-                continue
-            n = int(torch.randint(0, 90, (1,), generator=g)) if (s + t) % 5 else 0
-            if n == 0:
-                pairs[f"{s}_{t}"] = {"source_coords": None if s % 2 else torch.zeros(0, 2), "target_coords": None,
-                                     "cos_sims": None, "r": None}
-                continue
-            xy = lambda: torch.stack([torch.rand(n, generator=g) * (W - 15) + 7, torch.rand(n, generator=g) * (H - 15) + 7], 1)
-            pairs[f"{s}_{t}"] = {"source_coords": xy(), "target_coords": xy(), "cos_sims": torch.rand(n, generator=g) * 1.2 - 0.2,
-                                 "r": torch.rand(n, generator=g)}
-    frames_set_t = torch.tensor([0, 2, 3, 5], dtype=torch.int32)
-    emb = torch.randn(4, C, h, w, generator=g) + 0.3
-    raw = emb + 0.1 * torch.randn(4, C, h, w, generator=g)
-
-    def model_like(tracker_cls, e):
-        m = types.SimpleNamespace()
-        m.video = torch.zeros(FRAMES, 3, H, W)
-        m.dino_patch_size, m.stride, m.device = 14, 7, "cpu"
-        m.frame_embeddings = e.clone().requires_grad_(True)
-        m.raw_embeddings = raw
-        m._refined = m._dino = None
-        m.normalize_points_for_sampling = types.MethodType(tracker_cls.normalize_points_for_sampling, m)
-        m.sample_embeddings = types.MethodType(tracker_cls.sample_embeddings, m)
-        return m
-
+def world():
+    """The trainer class (make_trainer's subclass; the terms under test are its own methods, the reference base class
+    contributes none of them) without __init__: attributes set by hand, on the scene of ref_units.trainer_scene -- masks,
+    best buddies of every frame pair, a stand-in model holding the batch's embeddings."""
     from dino_tracker_amd.tracker import Tracker as OurTracker
-    theirs = object.__new__(ref_dt.DINOTracker)
-    ours = object.__new__(T.make_trainer(ref_dt.DINOTracker))
-    for o in (theirs, ours):
-        o.config, o.fg_masks, o.dino_bb_pairs = dict(CONFIG), fg_masks, pairs
-        o.of_loss_fn = torch.nn.HuberLoss(delta=1 / 32, reduction="none")
-    m_ours = model_like(OurTracker, emb)
+    fg_masks, pairs, frames_set_t, emb, raw, h, w = U.trainer_scene()
+    ours = object.__new__(T.make_trainer(object))
+    ours.config, ours.fg_masks, ours.dino_bb_pairs = dict(CONFIG), fg_masks, pairs
+    ours.of_loss_fn = torch.nn.HuberLoss(delta=1 / 32, reduction="none")
+    m_ours = U.trainer_model_like(OurTracker, emb, raw)
     ours.prepare_tables(m_ours)
-    return types.SimpleNamespace(ref=ref, ref_dt=ref_dt, theirs=theirs, ours=ours, m_theirs=model_like(ref.tracker.Tracker, emb),
-                                 m_ours=m_ours, frames_set_t=frames_set_t, pairs=pairs, fg_masks=fg_masks, h=h, w=w)
-
-
-class Recorder:
-    """Records what torch.randint / torch.randperm return while the reference's methods run."""
-
-    def __init__(self, monkeypatch):
-        self.randint, self.randperm = [], []
-        ri, rp = torch.randint, torch.randperm
-
-        def randint(*a, **k):
-            out = ri(*a, **k)
-            self.randint.append(out.clone())
-            return out
-
-        def randperm(*a, **k):
-            out = rp(*a, **k)
-            self.randperm.append(out.clone())
-            return out
-
-        monkeypatch.setattr(torch, "randint", randint)
-        monkeypatch.setattr(torch, "randperm", randperm)
+    return types.SimpleNamespace(ours=ours, m_ours=m_ours, frames_set_t=frames_set_t, pairs=pairs, fg_masks=fg_masks, h=h, w=w)
 
 
 def _pad(rows, width):
@@ -114,16 +55,14 @@ def _close(a, b, tol=2e-5):
     assert abs(float(a) - float(b)) <= tol * max(abs(float(b)), 1e-3), (float(a), float(b))
 
 
-def test_dino_bb_contrastive_loss_matches_reference(world, monkeypatch):
+def test_dino_bb_contrastive_loss_matches_reference(world, gold):
     wd = world
-    torch.manual_seed(3)
-    rec = Recorder(monkeypatch)
-    want = wd.theirs.get_dino_bb_contrastive_loss(wd.m_theirs, wd.frames_set_t)
-    want.backward()
-    s_sel, t_sel = rec.randint[0], rec.randint[-1]          # the target selectors are re-drawn until none equals its source
+    want, g_want = gold["trainer_dino_bb_value"], torch.from_numpy(gold["trainer_dino_bb_grad"])
+    randint = U.unragged(gold, "trainer_dino_bb_randint")
+    s_sel, t_sel = randint[0], randint[-1]          # the target selectors are re-drawn until none equals its source
     n_fg, n_bg = wd.ours.split_counts(CONFIG["cl_points_per_pair"], CONFIG["cl_fg_points_ratio"])
     tb = wd.ours._bb_table
-    rows, perms = [], iter(rec.randperm)
+    rows, perms = [], iter(U.unragged(gold, "trainer_dino_bb_randperm"))
     used_pairs = 0
     for s_i, t_i in zip(s_sel.tolist(), t_sel.tolist()):
         s_f, t_f = int(wd.frames_set_t[s_i]), int(wd.frames_set_t[t_i])
@@ -132,8 +71,7 @@ def test_dino_bb_contrastive_loss_matches_reference(world, monkeypatch):
             rows.append(torch.zeros(0, dtype=torch.long))
             continue
         used_pairs += 1
-        _, _, fg = wd.ref.models_utils.filter_bb_foreground_pairs(bb["source_coords"], bb["target_coords"], wd.fg_masks[s_f],
-                                                                  resw=W, resh=H)
+        fg = torch.from_numpy(gold[f"trainer_fg_{s_f}_{t_f}"])   # models/utils.py filter_bb_foreground_pairs of the reference
         slot = int(tb.slot[s_f * FRAMES + t_f])
         assert slot >= 0 and int(tb.cnt[slot]) == fg.shape[0]
         base = int(tb.off[slot])
@@ -145,21 +83,19 @@ def test_dino_bb_contrastive_loss_matches_reference(world, monkeypatch):
     got = wd.ours.dino_bb_terms(wd.m_ours, s_sel, t_sel, picks, ok)
     got.backward()
     _close(got, want)
-    g_want, g_got = wd.m_theirs.frame_embeddings.grad, wd.m_ours.frame_embeddings.grad
+    g_got = wd.m_ours.frame_embeddings.grad
     assert (g_got - g_want).abs().max() <= 2e-5 * g_want.abs().max()
 
 
-def test_refined_bb_contrastive_loss_matches_reference(world, monkeypatch):
+def test_refined_bb_contrastive_loss_matches_reference(world, gold):
     wd = world
-    torch.manual_seed(4)
-    rec = Recorder(monkeypatch)
-    want = wd.theirs.get_refiner_contrastive_loss(wd.m_theirs, wd.frames_set_t)
-    want.backward()
-    s_sel, t_sel = rec.randint[0], rec.randint[1]
+    want, g_want = gold["trainer_refined_bb_value"], torch.from_numpy(gold["trainer_refined_bb_grad"])
+    randint = U.unragged(gold, "trainer_refined_bb_randint")
+    s_sel, t_sel = randint[0], randint[1]
     n_fg, n_bg = wd.ours.split_counts(CONFIG["cl_points_per_pair"], CONFIG["cl_fg_points_ratio"])
     nn_st, nn_ts = T.mutual_argmax(wd.m_ours.frame_embeddings.detach(), s_sel, t_sel)
     cells = torch.arange(nn_st.shape[1])
-    perms = iter(rec.randperm)
+    perms = iter(U.unragged(gold, "trainer_refined_bb_randperm"))
     src_rows, tgt_rows = [], []
     for p in range(s_sel.shape[0]):
         mutual = nn_ts[p][nn_st[p]] == cells
@@ -176,7 +112,7 @@ def test_refined_bb_contrastive_loss_matches_reference(world, monkeypatch):
     got = wd.ours.refined_bb_terms(wd.m_ours, s_sel, t_sel, src_cells, tgt_cells, ok)
     got.backward()
     _close(got, want)
-    g_want, g_got = wd.m_theirs.frame_embeddings.grad, wd.m_ours.frame_embeddings.grad
+    g_got = wd.m_ours.frame_embeddings.grad
     assert (g_got - g_want).abs().max() <= 2e-5 * g_want.abs().max()
 
 
@@ -233,24 +169,15 @@ def test_joint_contrastive_evaluation_equals_the_separate_terms(world):
     _close(j_ref3, wd.ours.refined_bb_terms(wd.m_ours, *wide_ref), 1e-6)
 
 
-def test_regularisation_tracking_and_cycle_terms_match_reference(world):
+def test_regularisation_tracking_and_cycle_terms_match_reference(world, gold):
     wd = world
-    want_n = wd.theirs.get_emb_norm_regularization_loss(wd.m_theirs)
-    want_a = wd.theirs.get_emb_angle_regularization_loss(wd.m_theirs)
     got_n, got_a = T.emb_regularization_terms(wd.m_ours.frame_embeddings, wd.m_ours.raw_embeddings)
-    _close(got_n, want_n, 1e-6)
-    _close(got_a, want_a, 1e-6)
-    g = torch.Generator().manual_seed(6)
-    x, y = torch.randn(50, 2, generator=g) * 0.05, torch.randn(50, 2, generator=g) * 0.05
-    _close(T.weighted_mean(T.huber(x, y), torch.ones(50, dtype=torch.bool)), wd.theirs.of_loss_fn(x, y).mean(), 1e-6)
-    keep = torch.rand(50, generator=g) > 0.4
-    preds = {"source_coords": torch.randn(50, 3, generator=g), "target_coords": torch.randn(50, 3, generator=g),
-             "source_target_coords": torch.randn(50, 2, generator=g), "target_source_coords": torch.randn(50, 2, generator=g),
-             "cycle_consistency_dists": torch.rand(50, generator=g) * 4}
-    kept = {k: v[keep] for k, v in preds.items()}
-    m_t = types.SimpleNamespace(get_cycle_consistent_preds=lambda frames, masks: kept)
+    _close(got_n, gold["trainer_emb_norm"], 1e-6)
+    _close(got_a, gold["trainer_emb_angle"], 1e-6)
+    x, y, keep, preds = U.cycle_case()
+    _close(T.weighted_mean(T.huber(x, y), torch.ones(50, dtype=torch.bool)), gold["trainer_huber_mean"], 1e-6)
     m_o = types.SimpleNamespace(get_cycle_consistency_terms=lambda frames, masks: dict(preds, keep=keep))
-    _close(wd.ours.cycle_terms(m_o, wd.frames_set_t), wd.theirs.get_cycle_consistency_loss(m_t, (None, wd.frames_set_t)), 1e-6)
+    _close(wd.ours.cycle_terms(m_o, wd.frames_set_t), gold["trainer_cycle"], 1e-6)
 
 
 def test_key_sampling_is_uniform_without_replacement():
