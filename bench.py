@@ -3,6 +3,7 @@
 
     python bench.py --gpus N --steps K --warmup W         (N > 1 spawns its own ranks when WORLD_SIZE is unset)
     python bench.py ... --dump-outputs DIR                (also writes the last timed step's results to DIR/*.npy)
+    python bench.py ... --full                            (also every leg beyond the headline: see below)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -13,6 +14,13 @@ A "step" = one pass of the hot path (P1 ViT features -> P2 Delta-DINO refinement
   * --mode query-parallel (strong scaling on ONE video, SURVEY 8e level 2): frames split over the ranks for P1 / P2,
     one all-gather of the refined volume, queries split over the ranks for P3, one gather of the results.
 Metric: query-points*frames/s = videos * N * T * K / wall (max over ranks).  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line.  --full adds, after the
+timed region and without touching it, every other leg: the shader clock / board power over repeated steps, the
+30-video batch (`videos30`), the per-kernel pass (`roofline`, with the live PMC child passes), the CPU baseline and the
+parity legs against the oracle, and the test-time-training children (`train`); the --no-* switches drop single legs
+of a --full run.  A plain run prints `videos30`, `roofline`, `clock_power`, `cpu_baseline` and `parity_sample` as null
+and no `train` key.
 """
 import argparse
 import json
@@ -53,6 +61,9 @@ def parse():
     ap.add_argument("--features", default="vit", choices=["vit", "synthetic"],
                     help="vit: features come from the (random-weight) ViT on the synthetic video; synthetic: the "
                          "feature-level generator with dense anchors (worst case for the tracker stage)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beyond the headline after the timed region (clock / power, videos30, roofline, CPU "
+                         "baseline and parity, train); a plain run only sets up, warms up, times and prints the line")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-clock-power", action="store_true", help="skip the shader-clock / board-power sampling legs")
     ap.add_argument("--no-live-traffic", action="store_true", help="skip the two rocprofv3 PMC child passes that measure roofline.traffic live")
@@ -339,7 +350,7 @@ def main():
     # shader clock / board power of whole steps: sampled over a REPEAT of the steps after the timed region (the polling thread
     # shares the interpreter with the launch loop; the timed region stays untouched)
     sampler = clock_power = None
-    if rank == 0 and world == 1 and not args.no_clock_power:
+    if args.full and rank == 0 and world == 1 and not args.no_clock_power:
         sys.path.insert(0, os.path.join(ROOT, "scripts"))
         from power_sampler import PowerSampler
         sampler = PowerSampler(local).start()
@@ -365,10 +376,10 @@ def main():
     frames_per_step = sum(batch_lengths) if batch_lengths is not None else videos_per_step * T   # query-points x FRAMES: ragged batches count their own
 
     # ---- north_star's strong-scaling form in the SAME line: a batch of 30 videos sharded v = r (mod world),
-    # 4/4/4/4/4/4/3/3 on 8 ranks, one RCCL gather per round; a second timed phase (one step, the kernels are warm) so that the
-    # driver's plain `bench.py --gpus N` runs also carry the number north_star's ">= 6x at 8 GPUs on a 30-video batch" is about
+    # 4/4/4/4/4/4/3/3 on 8 ranks, one RCCL gather per round; a second timed phase (one step, the kernels are warm) so that
+    # `bench.py --gpus N --full` also carries the number north_star's ">= 6x at 8 GPUs on a 30-video batch" is about
     videos30 = None
-    if args.videos == 0 and not qpar and not args.no_videos30 and stages == ["extract", "refine", "track"] and args.features == "vit":
+    if args.full and args.videos == 0 and not qpar and not args.no_videos30 and stages == ["extract", "refine", "track"] and args.features == "vit":
         V30 = 30
 
         def timed(fn):
@@ -414,10 +425,12 @@ def main():
     pairs = int(mi.last_counts[0]) if hasattr(mi, "last_counts") else 0
     maps = N * T + pairs * T
     tiers = dict(trk.last_track_stats) if trk.last_track_stats else None   # the anchor-stage dtk_track call
-    ops.profile_enable(True)
-    one_video(videos[0])
-    prof = ops.profile_collect()
-    ops.profile_enable(False)
+    prof = None
+    if args.full:
+        ops.profile_enable(True)
+        one_video(videos[0])
+        prof = ops.profile_collect()
+        ops.profile_enable(False)
     roofline = None
     if prof:
         HW, S = 67 * 121, 67 * 121 + 1
@@ -566,7 +579,7 @@ def main():
     #     cpu_qpf = N T / (T t_vit + T t_delta + N t_query).
     # The same K queries are then tracked by the HIP path on the same refined volume: `parity_sample`.
     cpu = parity = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and "track" in stages:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and "track" in stages:
         from oracle import ref_algo as A
         nq = max(1, min(N, args.cpu_queries))
         npar = max(nq, min(N, args.cpu_parity_queries))
@@ -763,9 +776,9 @@ def main():
                        "parallelism": (f"query-parallel x{world} (frames split for P1/P2, queries for P3)" if qpar
                                        else f"video-parallel x{world}")},
             "videos30": videos30, "per_rank": per_rank, "roofline": roofline, "clock_power": clock_power, "cpu_baseline": cpu, "parity_sample": parity,
-            "dump_outputs": dumped,
+            "dump_outputs": dumped, "full": args.full,
         }
-        if world == 1 and not args.no_train:
+        if args.full and world == 1 and not args.no_train:
             out["train"] = train_leg(args)
         print(json.dumps(out), flush=True)
     if world > 1:
