@@ -152,6 +152,11 @@ SIGNATURES = {
     "dtk_bb_nms_workspace_bytes": (c_size_t, [ctypes.POINTER(Geom), c_int]),
     "dtk_bb_nms": (c_int, [ctypes.POINTER(Geom), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_int,
                            c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
+    "dtk_traj_start_fg": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "dtk_nearest_traj_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "dtk_nearest_traj": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "dtk_of_filter_keep": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_float, c_float, c_void_p, c_void_p,
+                                   c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "dtk_feat_f16_bytes": (c_size_t, [ctypes.POINTER(Geom)]),
     "dtk_make_feat_f16": (c_int, [ctypes.POINTER(Geom), c_void_p, c_void_p, c_void_p, c_void_p]),
     "dtk_traj_cos_sims": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),

@@ -177,6 +177,60 @@ def bb_nms(g: Geom, feat: torch.Tensor, norms: torch.Tensor, emb: torch.Tensor, 
     return peak, r
 
 
+def _check_traj(traj: torch.Tensor) -> Tuple[int, int]:
+    if traj.dim() != 3 or traj.shape[2] != 2:
+        raise RuntimeError(f"dino_tracker_amd: trajectories must be [N, T, 2], got {tuple(traj.shape)}")
+    if traj.shape[0] >= 2 ** 31 - 1 or traj.shape[1] == 0:
+        raise RuntimeError(f"dino_tracker_amd: unsupported trajectory shape {tuple(traj.shape)}")
+    return int(traj.shape[0]), int(traj.shape[1])
+
+
+def traj_start_fg(traj: torch.Tensor, masks: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """dtk_traj_start_fg: (fg [N] bool, err [1] int32) -- the mask at each trajectory's first tracked point, rounded half to
+    even; err counts the rows without a defined reference result (no tracked frame, start point outside the mask)."""
+    N, T = _check_traj(traj)
+    if masks.dim() != 3:
+        raise RuntimeError(f"dino_tracker_amd: masks must be [T, H, W], got {tuple(masks.shape)}")
+    Tm, H, W = masks.shape
+    fg = torch.empty(N, dtype=torch.uint8, device=traj.device)
+    err = torch.empty(1, dtype=torch.int32, device=traj.device)
+    check(lib().dtk_traj_start_fg(_p(traj, torch.float32), N, T, _p(masks, torch.uint8), Tm, H, W, _p(fg), _p(err), _stream()))
+    return fg.bool(), err
+
+
+def nearest_traj(traj: torch.Tensor, gh: int, gw: int, origin: float, stride: float) -> torch.Tensor:
+    """dtk_nearest_traj: idx [T, gh * gw] int32, the first trajectory at the least fp32 distance from every grid point."""
+    N, T = _check_traj(traj)
+    idx = torch.empty((T, gh * gw), dtype=torch.int32, device=traj.device)
+    nb = int(lib().dtk_nearest_traj_workspace_bytes(N, T, gh, gw))
+    ws = torch.empty(nb, dtype=torch.uint8, device=traj.device)
+    check(lib().dtk_nearest_traj(_p(traj, torch.float32), N, T, gh, gw, float(origin), float(stride), _p(idx), _p(ws), nb,
+                                 _stream()))
+    return idx
+
+
+def of_filter_keep(traj: torch.Tensor, idx: torch.Tensor, gh: int, gw: int, origin: float, stride: float, src: torch.Tensor,
+                   tgt: torch.Tensor, pair_off: torch.Tensor, pair_st: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """dtk_of_filter_keep: (keep [M] bool, err [1] int32) for the best buddies of P frame pairs, concatenated (src / tgt [M, 2],
+    pair_off [P + 1], pair_st [P, 2] = (source frame, target frame))."""
+    N, T = _check_traj(traj)
+    if N == 0:
+        raise RuntimeError("dino_tracker_amd: the optical-flow filter needs at least one trajectory")
+    if idx.shape != (T, gh * gw):
+        raise RuntimeError(f"dino_tracker_amd: idx must be [{T}, {gh * gw}], got {tuple(idx.shape)}")
+    M, P = src.shape[0], pair_st.shape[0]
+    if src.shape != (M, 2) or tgt.shape != (M, 2) or pair_off.shape != (P + 1,) or pair_st.shape != (P, 2):
+        raise RuntimeError("dino_tracker_amd: of_filter_keep: inconsistent src / tgt / pair_off / pair_st shapes")
+    if P and not bool((pair_off[0] == 0) & (pair_off[-1] == M) & (pair_off[1:] >= pair_off[:-1]).all()):
+        raise RuntimeError(f"dino_tracker_amd: of_filter_keep: pair_off must rise from 0 to {M}")
+    keep = torch.empty(M, dtype=torch.uint8, device=traj.device)
+    err = torch.empty(1, dtype=torch.int32, device=traj.device)
+    check(lib().dtk_of_filter_keep(_p(traj, torch.float32), N, T, _p(idx, torch.int32), gh, gw, float(origin), float(stride),
+                                   _p(src, torch.float32) if M else None, _p(tgt, torch.float32) if M else None,
+                                   _p(pair_off, torch.int32), _p(pair_st, torch.int32), P, _p(keep), _p(err), _stream()))
+    return keep.bool(), err
+
+
 def traj_cos_sims(S: torch.Tensor, tq: torch.Tensor, N: int, T: int) -> torch.Tensor:
     C = S.shape[-1]
     cs = torch.empty((N, T), dtype=torch.float32, device=S.device)

@@ -371,6 +371,35 @@ int dtk_bb_nms(const dtk_geom* g, const float* feat, const float* norms, const f
                const int32_t* tgt, float box_size, float iou_thresh, int topk, float* peak_affs, float* r, int M,
                void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- optical-flow trajectory preprocessing (SURVEY 8f N1 inputs) --------------------------------------------------------
+ * Trajectories traj [N][T][2] fp32 (x, y), NaN where a point is not tracked (untracked = either coordinate NaN).
+ *
+ * fg / bg split (preprocessing/split_trajectories_to_fg_bg.py:61-67): per row n the first frame s with a tracked point,
+ * the point rounded half-to-even (torch.round), fg[n] = masks[s][y][x] > 0 (masks [Tm][H][W] uint8).  Rows with no tracked
+ * frame, or whose start point rounds outside the mask (or s >= Tm), get fg[n] = 0 and are counted in *err (device int32,
+ * zeroed by the call): the reference would index with NaN-cast or wrapping indices there. */
+int dtk_traj_start_fg(const float* traj, int N, int T, const uint8_t* masks, int Tm, int H, int W, uint8_t* fg, int32_t* err,
+                      void* stream);
+
+/* Nearest trajectory of every token-grid point in every frame (preprocessing_dino_bb/of_filter_dino_best_buddies.py:9-29,
+ * :50-54): grid point g = (origin + stride * (g % gw), origin + stride * (g / gw)) -- dino_bb_utils.create_meshgrid with
+ * origin = patch / 2 --, idx[t][g] = argmin over n of |traj[n][t] - g| compared as (d^2 in fp32, n) lexicographically: the
+ * lowest n on equal distances (torch's first-index rule), untracked points = +inf, 0 when frame t has no tracked point.
+ * Workspace: dtk_nearest_traj_workspace_bytes (the compacted tracked points of every frame, worst case N per frame). */
+size_t dtk_nearest_traj_workspace_bytes(int N, int T, int gh, int gw);
+int dtk_nearest_traj(const float* traj, int N, int T, int gh, int gw, float origin, float stride, int32_t* idx,
+                     void* workspace, size_t workspace_bytes, void* stream);
+
+/* Optical-flow filter of the best buddies of all frame pairs in one call (of_filter_dino_best_buddies.py:83-94).  Pair p is
+ * frames (pair_st[2p], pair_st[2p+1]) = (s, t) with entries pair_off[p] .. pair_off[p+1] of src / tgt ([M][2] pixel (x, y)).
+ * cell = ((xy - origin) // stride) (torch float floor division), ns = idx[s][cell(src)], nt = idx[t][cell(tgt)] (idx from
+ * dtk_nearest_traj on the same grid), keep[e] = traj[ns][t] untracked AND traj[nt][s] untracked -- the reference's sense: it
+ * keeps the buddies whose flow trajectory is lost.  Entries whose cell lies outside the grid (or whose frames are outside
+ * [0, T)) get keep 0 and are counted in *err (device int32, zeroed by the call). */
+int dtk_of_filter_keep(const float* traj, int N, int T, const int32_t* idx, int gh, int gw, float origin, float stride,
+                       const float* src, const float* tgt, const int32_t* pair_off, const int32_t* pair_st, int P,
+                       uint8_t* keep, int32_t* err, void* stream);
+
 /* 16-bit copies of the feature volume consumed by DTK_TRACK_MFMA (C % 32 == 0), one buffer of dtk_feat_f16_bytes(g):
  *   - f16[t][row][col][c] = 32 F/|F|, every map row padded with zero cells to a multiple of 128 columns (an N-tile of the
  *     candidate GEMM is one map row);
