@@ -94,6 +94,28 @@ __device__ __forceinline__ float wave_max(float v) {
 __device__ __forceinline__ int wave_sum_i(int v) {
     return wave_allreduce_bits(v, [](int a, int b) { return a + b; });
 }
+// MODE register bit 23 (FP16_OVFL): an fp16 result that overflows is clamped to +-65504 instead of becoming +-inf
+// (conversions included), so that a rare out-of-range activation saturates instead of poisoning everything downstream.
+__device__ __forceinline__ void dtk_fp16_saturate_mode() { __builtin_amdgcn_s_setreg(1 | (23 << 6) | (0 << 11), 1); }
+// Wait until at most N of this wave's vector-memory requests are in flight.  The LDS-DMA requests below are asm statements, so
+// the compiler does not serialise them against the ds_reads of the OTHER buffer with a vmcnt(0) of its own -- and does not wait
+// for them either: a kernel awaits its requests with this before the barrier that publishes the tile.
+template <int N>
+__device__ __forceinline__ void dtk_vm_wait() { asm volatile("s_waitcnt vmcnt(%0)" ::"i"(N) : "memory"); }
+// LDS-DMA from a 64-bit per-lane global address: 16 bytes per lane into LDS at the wave-uniform `lds_dst` (+ 16 bytes per lane,
+// the hardware's lane-linear image), through m0, which is saved and restored inside the statement.
+__device__ __forceinline__ void dtk_glds16(const void* gsrc, unsigned lds_dst) {
+    unsigned keep;
+    asm volatile(
+        "s_mov_b32 %0, m0\n\t"
+        "s_mov_b32 m0, %2\n\t"
+        "s_nop 0\n\t"
+        "global_load_lds_dwordx4 %1, off\n\t"
+        "s_mov_b32 m0, %0"
+        : "=&s"(keep)
+        : "v"(gsrc), "s"(lds_dst)
+        : "memory");
+}
 // LDS-DMA through a buffer descriptor (round 4): global address = descriptor base + scalar byte offset (the tile: one SALU add
 // per request) + 32-bit per-lane offset (a VGPR that is constant for the whole kernel); LDS destination = wave-uniform scalar +
 // immediate (+ 16 bytes per lane, the hardware's lane-linear image).  Three issue slots per request; the global_load_lds form

@@ -495,12 +495,6 @@ constexpr float EPS_PK = 2.1e-3f;
 typedef float f16v __attribute__((ext_vector_type(16)));
 constexpr size_t peaks_lds_bytes(int cb) { return 3 * (size_t)(32 * cb) * 384 * 2 + 64; }   // three tiles + the frame range (dynamic LDS)
 
-// (LDS-DMA requests go through dtk_buffer_lds16, common.h; issued from asm so that the compiler does not serialise them against
-// the ds_reads of the OTHER buffer with a vmcnt(0) of its own: completion is awaited explicitly -- glds_wait -- before the
-// barrier that publishes the tile.)
-template <int N>
-__device__ __forceinline__ void glds_wait() { asm volatile("s_waitcnt vmcnt(%0)" ::"i"(N) : "memory"); }
-
 // Sorted top-6 insertion of one accumulator value as a program of eight VALU instructions: value -> key (fixed point -- the
 // accumulator already is 2^17 rho; negative values stay negative and never enter a list that starts at zero -- shifted above
 // the 13-bit position tag, which is wave-uniform: an SGPR operand), then one v_med3_i32 per list entry from the tail up and a
@@ -737,18 +731,18 @@ __global__ __launch_bounds__(256) void corr_peaks_kernel(dtk_geom g, const half_
         // the end are clamped to the last one (never read), which keeps that count uniform.
         issue(0, 0);
         issue(min(1, NT - 1), 1);
-        glds_wait<NL * CB>();
+        dtk_vm_wait<NL * CB>();
         __syncthreads();
         int n = 0, b0 = 0;  // b0 = n % 3
         for (; n + 1 < NT; n += 2) {
             const int b1 = b0 == 2 ? 0 : b0 + 1, b2 = b1 == 2 ? 0 : b1 + 1;
             issue(min(n + 2, NT - 1), b2);
             step(b0, accA, accB, max(n - 1, 0));  // first step: accB = 0, pushes zeros
-            glds_wait<NL * CB>();
+            dtk_vm_wait<NL * CB>();
             __syncthreads();
             issue(min(n + 3, NT - 1), b0);
             step(b1, accB, accA, n);
-            glds_wait<NL * CB>();
+            dtk_vm_wait<NL * CB>();
             __syncthreads();
             b0 = b2;
         }
@@ -758,7 +752,7 @@ __global__ __launch_bounds__(256) void corr_peaks_kernel(dtk_geom g, const half_
         } else {
             epi(accB, n - 1);
         }
-        glds_wait<0>();
+        dtk_vm_wait<0>();
         __syncthreads();  // every wave is done with the buffers before the next frame restages them
         // merge the two lane halves of each source and write its record
 #pragma unroll
@@ -960,7 +954,7 @@ __global__ __launch_bounds__(256) void corr_peaks_wide_kernel(dtk_geom g, const 
                 }
                 __builtin_amdgcn_sched_barrier(0);
             });
-            glds_wait<0>();      // the next tile has landed (this wave's requests; the barrier covers the others')
+            dtk_vm_wait<0>();      // the next tile has landed (this wave's requests; the barrier covers the others')
             __syncthreads();     // barrier A: the tile is published, `buf` and the exchange slots are free
         };
         // the last tile's partials: no MFMAs to hide under
@@ -976,7 +970,7 @@ __global__ __launch_bounds__(256) void corr_peaks_wide_kernel(dtk_geom g, const 
         };
         f16v accA[2], accB[2];
         issue(0);
-        glds_wait<0>();
+        dtk_vm_wait<0>();
         __syncthreads();
         int n = 0;
         for (; n + 1 < NT; n += 2) {

@@ -21,31 +21,10 @@
 #include <stdlib.h>
 #include <utility>
 #include "common.h"
-
-#define ATT2_NS att2_f16
-#define ATT2_T _Float16
-#define ATT2_F16 1
-#define ATT2_MFMA __builtin_amdgcn_mfma_f32_32x32x16_f16
 #include "vit_attention2.h"
 #include "vit_attention4.h"
 #include "vit_attention5.h"
 #include "vit_attention6.h"
-#undef ATT2_NS
-#undef ATT2_T
-#undef ATT2_F16
-#undef ATT2_MFMA
-#define ATT2_NS att2_bf16
-#define ATT2_T __bf16
-#define ATT2_F16 0
-#define ATT2_MFMA __builtin_amdgcn_mfma_f32_32x32x16_bf16
-#include "vit_attention2.h"
-#include "vit_attention4.h"
-#include "vit_attention5.h"
-#include "vit_attention6.h"
-#undef ATT2_NS
-#undef ATT2_T
-#undef ATT2_F16
-#undef ATT2_MFMA
 
 namespace {
 
@@ -68,7 +47,7 @@ __device__ __forceinline__ f4 mfma16(bf8 a, bf8 b, f4 c) { return __builtin_amdg
 __device__ __forceinline__ f16v mfma32(h8 a, h8 b, f16v c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
 __device__ __forceinline__ f16v mfma32(bf8 a, bf8 b, f16v c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
 template <typename T> __device__ __forceinline__ void operand_mode() {
-    if (IsF16<T>::value) att2c::fp16_saturate_mode();  // overflowing fp16 results clamp to +-65504 instead of +-inf
+    if (IsF16<T>::value) dtk_fp16_saturate_mode();  // overflowing fp16 results clamp to +-65504 instead of +-inf
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -539,26 +518,12 @@ constexpr int WS_PITCH = 144;                    // staging row pitch: 128 B of 
 constexpr int WS_UNIT_BYTES = WS_ROWS * WS_PITCH;  // staging unit: 32 rows x 128 B (64 bf16 or 32 fp32 outputs)
 typedef float f2 __attribute__((ext_vector_type(2)));
 
-__device__ __forceinline__ void ws_glds16(const void* gsrc, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %2\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, off\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(gsrc), "s"(lds_dst)
-        : "memory");
-}
-template <int N>
-__device__ __forceinline__ void ws_wait() { asm volatile("s_waitcnt vmcnt(%0)" ::"i"(N) : "memory"); }
-
 // One wave's share of a pipeline stage of the wide GEMMs by DESCRIPTOR LDS-DMA (round 6; common.h dtk_buffer_lds16: three issue
-// slots per request where the global_load_lds form above costs ~13 -- 64-bit address arithmetic on the VALU, m0 saved and restored).
+// slots per request where the global_load_lds form, dtk_glds16, costs ~13 -- 64-bit address arithmetic on the VALU, m0 saved and
+// restored).
 // Request i of wave w lands at stage + (w REQ + i) KB: the stages of gemm_wide_delta / gemm_wide / gemm_split_dma are laid out so.
 // srd[i] = descriptor over the first row of the request's operand tile, voff[i] = the lane's constant byte offset in it (row, swizzled
-// piece), soff = the k-step's byte offset.  A kernel that calls this must not use ws_glds16 (m0: tests/test_abi.py::test_m0_users).
+// piece), soff = the k-step's byte offset.  A kernel that calls this must not use dtk_glds16 (m0: tests/test_abi.py::test_m0_users).
 template <int REQ, int I = 0>
 __device__ __forceinline__ void wd_issue(const dtk_u4 (&srd)[REQ], const unsigned (&voff)[REQ], unsigned soff, unsigned lds_dst) {
     dtk_buffer_lds16<I * 1024>(srd[I], soff, voff[I], lds_dst);
@@ -706,7 +671,7 @@ __global__ __launch_bounds__(512, 2) void gemm_wide_delta_kernel(const T* __rest
     const unsigned b_off = WD_A_BYTES + ((wc * 96 + fj) * 4 + (fg ^ fsw)) * 16;
     issue(0, 0);
     issue(1, 1);
-    ws_wait<WD_REQ>();  // stage 0 landed (stage 1 may still fly)
+    dtk_vm_wait<WD_REQ>();  // stage 0 landed (stage 1 may still fly)
     __syncthreads();
     int buf = 0;
     for (int ks = 0; ks < nk; ++ks) {
@@ -728,11 +693,11 @@ __global__ __launch_bounds__(512, 2) void gemm_wide_delta_kernel(const T* __rest
                         mfma16(bfr, af[mi], acc[half * 4 + mi][ni]);   // (W tile) x (token tile)^T: D transposed (round 5), see the epilogue
             }
         }
-        ws_wait<WD_REQ>();  // stage ks + 1 landed; the requests of ks + 2 stay in flight
+        dtk_vm_wait<WD_REQ>();  // stage ks + 1 landed; the requests of ks + 2 stay in flight
         __syncthreads();
         buf = buf == 2 ? 0 : buf + 1;
     }
-    ws_wait<0>();
+    dtk_vm_wait<0>();
     // D tiles are TRANSPOSED (round 5): lane (fg, fj) holds features 4 fg + r (r = 0..3) of token fj of each 16 x 16 tile -- four
     // consecutive features of one token: ONE 8-byte store per tile and lane (48 per lane and 256 x 384 tile) where the
     // token-major form needed four 2-byte stores (192)
@@ -940,7 +905,7 @@ __global__ __launch_bounds__(512, 2) void gemm_wide_kernel(const T* __restrict__
     issue(0, 0);
     issue(1, 1);
     issue(2, 2);
-    ws_wait<2 * W2_REQ>();  // stage 0 landed
+    dtk_vm_wait<2 * W2_REQ>();  // stage 0 landed
     __syncthreads();
     int buf = 0;
     if (PIPE) {
@@ -977,7 +942,7 @@ __global__ __launch_bounds__(512, 2) void gemm_wide_kernel(const T* __restrict__
                 // (this wave's reads of the current stage have returned before it passes the barrier: the DMA requests of the next
                 //  step overwrite the stage that was current one step earlier)
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                ws_wait<2 * W2_REQ>();  // stage ks + 1 landed; ks + 2 and ks + 3 stay in flight
+                dtk_vm_wait<2 * W2_REQ>();  // stage ks + 1 landed; ks + 2 and ks + 3 stay in flight
                 __syncthreads();
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {   // (behind the last step: the repeated last stage, harmless)
@@ -1012,12 +977,12 @@ __global__ __launch_bounds__(512, 2) void gemm_wide_kernel(const T* __restrict__
                         mfma16(bfr, af[mi], acc[half * 4 + mi][ni]);   // (W tile) x (token tile)^T: D transposed, see the epilogue
             }
         }
-        ws_wait<2 * W2_REQ>();  // stage ks + 1 landed; ks + 2 and ks + 3 stay in flight
+        dtk_vm_wait<2 * W2_REQ>();  // stage ks + 1 landed; ks + 2 and ks + 3 stay in flight
         __syncthreads();
         buf = (buf + 1) & 3;
     }
     }
-    ws_wait<0>();
+    dtk_vm_wait<0>();
     // D tiles are TRANSPOSED (the MFMAs above multiply (W tile) x (token tile)^T): lane (fg, fj) holds features 4 fg + r of token fj
     float amax = 0.f;
     if (PIPE && EPI != EPI_QKV) {
@@ -1238,7 +1203,7 @@ __global__ __launch_bounds__(256) void gemm_ws_kernel(const T* __restrict__ A, c
             const T* gp = A + m * WS_K + ((l_pp - g) & 15) * 8;
 #pragma unroll
             for (int c = 0; c < 3; ++c)
-                ws_glds16(gp + c * 128, __builtin_amdgcn_readfirstlane(lds_base + buf * WS_TILE_BYTES + (g * 3 + c) * 1024));
+                dtk_glds16(gp + c * 128, __builtin_amdgcn_readfirstlane(lds_base + buf * WS_TILE_BYTES + (g * 3 + c) * 1024));
         }
     };
     // B-operand fragment of k-step ks for lane (token j, half h): piece 2 ks + h -> region column c = ks >> 3
@@ -1376,18 +1341,18 @@ __global__ __launch_bounds__(256) void gemm_ws_kernel(const T* __restrict__ A, c
     // count, so vmcnt(LQ) -- the requests of the tile after next -- is sufficient, if conservative.
     issue(0, 0);
     issue(min(1, NT - 1), 1);
-    ws_wait<WS_LQ>();
+    dtk_vm_wait<WS_LQ>();
     __syncthreads();
     int n = 0, b0 = 0;
     for (; n + 1 < NT; n += 2) {
         const int b1 = b0 == 2 ? 0 : b0 + 1, b2 = b1 == 2 ? 0 : b1 + 1;
         issue(min(n + 2, NT - 1), b2);
         step(b0, accA, accB, n > 0, n > 1);
-        ws_wait<WS_LQ>();
+        dtk_vm_wait<WS_LQ>();
         __syncthreads();
         issue(min(n + 3, NT - 1), b0);
         step(b1, accB, accA, true, n > 0);
-        ws_wait<WS_LQ>();
+        dtk_vm_wait<WS_LQ>();
         __syncthreads();
         b0 = b2;
     }
@@ -1403,7 +1368,7 @@ __global__ __launch_bounds__(256) void gemm_ws_kernel(const T* __restrict__ A, c
     }
     flush();
     amax_report<T, EPI>(amax, e.ovf);
-    ws_wait<0>();
+    dtk_vm_wait<0>();
 }
 
 #include "vit_split.h"
@@ -1524,60 +1489,42 @@ VitPlan vit_plan(const dtk_vit_model* m, int ph, int pw, int frames) {
 }
 
 
-// attention launch per operand type (the kernel lives in a per-type namespace of vit_attention2.h)
-template <typename T> struct Att;
-template <> struct Att<_Float16> {
-    static int launch(const _Float16* q, const _Float16* k, const _Float16* vt, _Float16* o, int S, int Sp, int heads, int D,
-                      int FH, int variant, hipStream_t st) {
-        int QB;
-        if (variant == 2) {
-            const unsigned grid = att2c::attention2_grid(FH, S, 1, &QB);
-            DTK_LAUNCH("vit_attention", (att2_f16::attention2_kernel<1>), dim3(grid), dim3(512), 0, st, q, k, vt, o, S, Sp,
-                       heads, D, FH, QB);
-        } else if (variant >= 5) {   // round-5 experiment (stand-alone stage only): two waves per SIMD; variant = 5 + its ablation bits
-            const unsigned grid = att2_f16::attention5_grid(FH, S, &QB);
-#define DTK_A5(V, ABLV)                                                                                                       \
-    if (variant == V)                                                                                                         \
-        DTK_LAUNCH("vit_attention", (att2_f16::attention5_kernel<ABLV>), dim3(grid), dim3(512), 0, st, q, k, vt, o, S, Sp, heads, D, \
+// attention launch (vit_run, dtk_vit_attention).  variant 2: attention2 (DTK_VIT_ATTENTION_V2 / DTK_OPERAND_ATTENTION_V2);
+// 4: attention4 (rounds 4-5: 64 queries per wave; DTK_VIT_ATTENTION_V4 / DTK_OPERAND_ATTENTION_V4); >= 5: attention5 (round-5
+// experiment, stand-alone stage only: two waves per SIMD; fp16: variant = 5 + its ablation bits, bf16: the full form whatever the
+// bits); anything else: attention6.
+template <typename T>
+int attention_launch(const T* q, const T* k, const T* vt, T* o, int S, int Sp, int heads, int D, int FH, int variant,
+                     hipStream_t st) {
+    int QB;
+    if (variant == 2) {
+        const unsigned grid = attn::attention_grid(FH, S, 256, &QB);
+        DTK_LAUNCH("vit_attention", (attn::attention2_kernel<T, 1>), dim3(grid), dim3(512), 0, st, q, k, vt, o, S, Sp, heads, D,
                    FH, QB);
+    } else if (variant >= 5) {
+        const unsigned grid = attn::attention_grid(FH, S, 512, &QB);
+        if constexpr (IsF16<T>::value) {
+#define DTK_A5(V, ABLV)                                                                                                   \
+    if (variant == V)                                                                                                     \
+        DTK_LAUNCH("vit_attention", (attn::attention5_kernel<T, ABLV>), dim3(grid), dim3(512), 0, st, q, k, vt, o, S, Sp, heads, \
+                   D, FH, QB);
             DTK_A5(5, 0) DTK_A5(6, 32) DTK_A5(7, 8 | 64) DTK_A5(8, 8 | 32 | 64) DTK_A5(9, 8 | 128) DTK_A5(10, 8 | 32 | 128)
 #undef DTK_A5
-        } else if (variant == 4) {   // rounds 4-5: 64 queries per wave (DTK_VIT_ATTENTION_V4 / DTK_OPERAND_ATTENTION_V4)
-            const unsigned grid = att2_f16::attention4_grid(FH, S, &QB);
-            DTK_LAUNCH("vit_attention", (att2_f16::attention4_kernel<0>), dim3(grid), dim3(256), 0, st, q, k, vt, o, S, Sp, heads,
-                       D, FH, QB);
         } else {
-            const unsigned grid = att2_f16::attention6_grid(FH, S, &QB);
-            DTK_LAUNCH("vit_attention", (att2_f16::attention6_kernel<0>), dim3(grid), dim3(256), 0, st, q, k, vt, o, S, Sp, heads,
+            DTK_LAUNCH("vit_attention", (attn::attention5_kernel<T, 0>), dim3(grid), dim3(512), 0, st, q, k, vt, o, S, Sp, heads,
                        D, FH, QB);
         }
-        return DTK_OK;
+    } else if (variant == 4) {
+        const unsigned grid = attn::attention_grid(FH, S, 256, &QB);
+        DTK_LAUNCH("vit_attention", (attn::attention4_kernel<T, 0>), dim3(grid), dim3(256), 0, st, q, k, vt, o, S, Sp, heads, D,
+                   FH, QB);
+    } else {
+        const unsigned grid = attn::attention_grid(FH, S, 128 * attn::A6_NQ, &QB);
+        DTK_LAUNCH("vit_attention", (attn::attention6_kernel<T, 0>), dim3(grid), dim3(256), 0, st, q, k, vt, o, S, Sp, heads, D,
+                   FH, QB);
     }
-};
-template <> struct Att<__bf16> {
-    static int launch(const __bf16* q, const __bf16* k, const __bf16* vt, __bf16* o, int S, int Sp, int heads, int D, int FH,
-                      int variant, hipStream_t st) {
-        int QB;
-        if (variant == 2) {
-            const unsigned grid = att2c::attention2_grid(FH, S, 1, &QB);
-            DTK_LAUNCH("vit_attention", (att2_bf16::attention2_kernel<1>), dim3(grid), dim3(512), 0, st, q, k, vt, o, S, Sp,
-                       heads, D, FH, QB);
-        } else if (variant >= 5) {
-            const unsigned grid = att2_bf16::attention5_grid(FH, S, &QB);
-            DTK_LAUNCH("vit_attention", (att2_bf16::attention5_kernel<0>), dim3(grid), dim3(512), 0, st, q, k, vt, o, S, Sp, heads,
-                       D, FH, QB);
-        } else if (variant == 4) {
-            const unsigned grid = att2_bf16::attention4_grid(FH, S, &QB);
-            DTK_LAUNCH("vit_attention", (att2_bf16::attention4_kernel<0>), dim3(grid), dim3(256), 0, st, q, k, vt, o, S, Sp,
-                       heads, D, FH, QB);
-        } else {
-            const unsigned grid = att2_bf16::attention6_grid(FH, S, &QB);
-            DTK_LAUNCH("vit_attention", (att2_bf16::attention6_kernel<0>), dim3(grid), dim3(256), 0, st, q, k, vt, o, S, Sp,
-                       heads, D, FH, QB);
-        }
-        return DTK_OK;
-    }
-};
+    return DTK_OK;
+}
 
 // |x| >= 65504 or non-finite anywhere in a 16-bit tensor -> *flag |= bit (DTK_VIT_CHECK_RANGE: every intermediate tensor)
 template <typename T>
@@ -1803,7 +1750,7 @@ int vit_run(const dtk_vit_model* m, const float* frames, int nframes, int video_
                            qkv_w, rows, 3 * D, D, e);
             }
             if (scan_all && scan_range(q, (long long)(p.ao - p.q) / 2, 2)) return DTK_E_HIP;
-            if (Att<T>::launch(q, k, vt, ao, S, Sp, m->heads, D, nf * m->heads, (m->flags & DTK_VIT_ATTENTION_V2) ? 2 : ((m->flags & DTK_VIT_ATTENTION_V4) ? 4 : 0), st)) return DTK_E_HIP;
+            if (attention_launch(q, k, vt, ao, S, Sp, m->heads, D, nf * m->heads, (m->flags & DTK_VIT_ATTENTION_V2) ? 2 : ((m->flags & DTK_VIT_ATTENTION_V4) ? 4 : 0), st)) return DTK_E_HIP;
             e = GemmEpi<T>{};
             e.bias = L.proj_b; e.delta = delta; e.gamma = L.ls1; e.no_store = dbg_ns;
             if (ws_ok) {
@@ -1937,12 +1884,12 @@ extern "C" int dtk_vit_attention(const void* q, const void* k, const void* vt, v
     operand_type &= ~(DTK_OPERAND_ATTENTION_V2 | DTK_OPERAND_ATTENTION_V4 | DTK_OPERAND_ATTENTION_V5 | DTK_OPERAND_ATTENTION_V5_INPHASE | 0x800 | 0x1000);
     DTK_REQUIRE(operand_type == DTK_OPERAND_F16 || operand_type == DTK_OPERAND_BF16, "dtk_vit_attention: operand_type");
     if (operand_type == DTK_OPERAND_BF16)
-        return Att<__bf16>::launch(reinterpret_cast<const __bf16*>(q), reinterpret_cast<const __bf16*>(k),
-                                   reinterpret_cast<const __bf16*>(vt), reinterpret_cast<__bf16*>(out), S, Sp, heads,
-                                   heads * 64, frames * heads, variant, dtk_stream(stream));
-    return Att<_Float16>::launch(reinterpret_cast<const _Float16*>(q), reinterpret_cast<const _Float16*>(k),
-                                 reinterpret_cast<const _Float16*>(vt), reinterpret_cast<_Float16*>(out), S, Sp, heads,
-                                 heads * 64, frames * heads, variant, dtk_stream(stream));
+        return attention_launch(reinterpret_cast<const __bf16*>(q), reinterpret_cast<const __bf16*>(k),
+                                reinterpret_cast<const __bf16*>(vt), reinterpret_cast<__bf16*>(out), S, Sp, heads, heads * 64,
+                                frames * heads, variant, dtk_stream(stream));
+    return attention_launch(reinterpret_cast<const _Float16*>(q), reinterpret_cast<const _Float16*>(k),
+                            reinterpret_cast<const _Float16*>(vt), reinterpret_cast<_Float16*>(out), S, Sp, heads, heads * 64,
+                            frames * heads, variant, dtk_stream(stream));
 }
 
 // The same stage on split operands (vit_split.h: the escalated precision): hi / lo planes of every operand and of the output.

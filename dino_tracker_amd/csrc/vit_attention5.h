@@ -1,7 +1,7 @@
 // vit_attention5.h -- flash attention for d_head = 64, EXPERIMENT of round 5: TWO waves per SIMD (8 waves per workgroup), 64
 // queries per wave, the two waves of a SIMD alternating a matrix phase and a vector phase.
 //
-// Include AFTER vit_attention4.h (same per-type namespace: tile layout, swizzle, guards, safe pass, helpers are reused).
+// Tile layout, swizzle, guards, safe pass and helpers are attention4's.
 // attention4 overlaps the MFMAs of one query tile with the softmax of the other INSIDE a wave (one wave per SIMD, 512 registers).
 // Here a wave has 256 registers and does one thing at a time; the overlap comes from its partner on the same SIMD:
 //     step      M_a(t): PV(1, t-1), S(0, t)      V_a(t): softmax(0, t); Vt fragments <- V(t);   request K(t+3)
@@ -16,24 +16,21 @@
 // V_b(t), two steps after the late half's V_a(t)... see the step table in DESIGN / NEGATIVE_RESULTS).
 // Guards as attention4 (RESC_T / POISON_T / LOW_T, safe pass); a tripped guard of query tile q is handled at the start of the wave's
 // next vector phase, when PV(q, t) has been issued and no score of q computed against the old reference is waiting.
-#ifndef ATT2_NS
-#error "include vit_attention2.h / vit_attention4.h first and keep ATT2_NS, ATT2_T, ATT2_F16, ATT2_MFMA defined"
-#endif
+#pragma once
+#include "vit_attention_common.h"
 
-namespace ATT2_NS {
-
-inline unsigned attention5_grid(int FH, int S, int* qb_out) {
-    const int QB = (S + 511) / 512;
-    *qb_out = QB;
-    return (unsigned)(((FH + 7) / 8) * 8 * QB);
-}
+namespace attn {
 
 // ABL (micro-benchmark): 8 = no guards / estimate, 32 = both halves in phase (no one-step delay of waves 4..7),
 // 64 = no vector work (exponentials, row sums, converts; refills and requests stay), 128 = no matrix work (the 16 MFMAs of a step)
-template <int ABL = 0>
-__global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) void attention5_kernel(const op_t* __restrict__ Q, const op_t* __restrict__ Kg,
-                                                            const op_t* __restrict__ Vt, op_t* __restrict__ O, int S, int Sp,
+template <typename T, int ABL = 0>
+__global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) void attention5_kernel(const T* __restrict__ Q, const T* __restrict__ Kg,
+                                                            const T* __restrict__ Vt, T* __restrict__ O, int S, int Sp,
                                                             int heads, int D, int FH, int QB) {
+    typedef Operand<T> Op;
+    typedef typename Op::v8 op8;
+    typedef typename Op::v4 op4;
+    typedef typename Op::v2 op2;
     __shared__ __attribute__((aligned(1024))) unsigned char tiles[A4_NB][TILE_BYTES];
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);          // 0..7
@@ -45,26 +42,26 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
     const int frame = fh / heads, head = fh - frame * heads;
     const int q0 = qb * 512 + w * 64;
     const int lq = lane & 31, hi = lane >> 5;
-    const op_t* Qb = Q + (size_t)fh * Sp * 64;
-    const op_t* Kb = Kg + (size_t)fh * Sp * 64;
-    const op_t* Vb = Vt + (size_t)fh * 64 * Sp;
-    if (F16) fp16_saturate_mode();
+    const T* Qb = Q + (size_t)fh * Sp * 64;
+    const T* Kb = Kg + (size_t)fh * Sp * 64;
+    const T* Vb = Vt + (size_t)fh * 64 * Sp;
+    if (Op::F16) dtk_fp16_saturate_mode();
 
     // DMA: wave w fills rows 8w .. 8w+7 of the K part and of the V^T part of a tile (one request each)
     const int lrow = w * 8 + (lane >> 3), lpc = (lane & 7) ^ ((lrow >> 1) & 7);
     const unsigned kvo = (unsigned)(lrow * 64 + lpc * 8) * 2u, vvo = (unsigned)(lrow * Sp + lpc * 8) * 2u;
     const unsigned lds_base = (unsigned)(size_t)&tiles[0][0];
     const int ntiles = (S + 63) / 64;
-    const u4v srd_k = make_srd(Kb), srd_v = make_srd(Vb);
+    const dtk_u4 srd_k = dtk_make_srd(Kb), srd_v = dtk_make_srd(Vb);
     const unsigned dst_k = __builtin_amdgcn_readfirstlane(lds_base + w * 1024);
     const unsigned dst_v = __builtin_amdgcn_readfirstlane(lds_base + 8192 + w * 1024);
     auto issue_k = [&](int t, auto buf_tag) {
         constexpr int BUF = decltype(buf_tag)::value;
-        buffer_lds16<BUF * TILE_BYTES>(srd_k, (unsigned)min(t, ntiles - 1) * 8192u, kvo, dst_k);
+        dtk_buffer_lds16<BUF * TILE_BYTES>(srd_k, (unsigned)min(t, ntiles - 1) * 8192u, kvo, dst_k);
     };
     auto issue_v = [&](int t, auto buf_tag) {
         constexpr int BUF = decltype(buf_tag)::value;
-        buffer_lds16<BUF * TILE_BYTES>(srd_v, (unsigned)min(t, ntiles - 1) * 128u, vvo, dst_v);
+        dtk_buffer_lds16<BUF * TILE_BYTES>(srd_v, (unsigned)min(t, ntiles - 1) * 128u, vvo, dst_v);
     };
     op8 qf[2][4];
 #pragma unroll
@@ -78,7 +75,7 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
 #pragma unroll
         for (int blk = 0; blk < 4; ++blk) {
             const int kr0 = blk < 2 ? blk * 32 : q0 + (blk - 2) * 32;
-            const op_t* kp = Kb + (size_t)min(kr0 + lq, Sp - 1) * 64 + hi * 8;
+            const T* kp = Kb + (size_t)min(kr0 + lq, Sp - 1) * 64 + hi * 8;
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks) kq[blk][ks] = *reinterpret_cast<const op8*>(kp + ks * 16);
         }
@@ -90,7 +87,7 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
 
     f16v o[2][2];   // O^T accumulators (AGPRs through mfma_acc_agpr)
     f16v sc[2];     // ONE score set: [key block]
-    u4v pf[4];      // ONE P^T set: [16-key group]
+    dtk_u4 pf[4];   // ONE P^T set: [16-key group]
     op8 kf[8], vf[8];
     float m_run[2] = {0.f, 0.f}, l_run[2] = {0.f, 0.f};
 #pragma unroll
@@ -125,7 +122,7 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
                 const int kb = blk < 2 ? blk : 2 + qt;
                 f16v so = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-                for (int ks = 0; ks < 4; ++ks) so = ATT2_MFMA(kq[kb][ks], qf[qt][ks], so, 0, 0, 0);
+                for (int ks = 0; ks < 4; ++ks) so = Op::mfma(kq[kb][ks], qf[qt][ks], so);
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int key = kr0 + (r & 3) + 8 * (r >> 2) + 4 * hi;
@@ -140,8 +137,8 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
 #pragma unroll
     for (int g = 0; g < 8; ++g)
 #pragma unroll
-        for (int e = 0; e < 8; ++e) vf[g][e] = (op_t)0.f;   // M_a(0) multiplies them with P = 0
-    vm_wait<0>();  // tiles 0 .. 2 have landed
+        for (int e = 0; e < 8; ++e) vf[g][e] = (T)0.f;   // M_a(0) multiplies them with P = 0
+    dtk_vm_wait<0>();  // tiles 0 .. 2 have landed
     __syncthreads();
 
 #pragma clang diagnostic push
@@ -160,9 +157,9 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
         float a, b;
         halves(lsum, a, b);
         const float tot = a + b;
-        if (!(a < POISON_T && b < POISON_T)) {
+        if (!(a < Op::POISON_T && b < Op::POISON_T)) {
             l_run[qt] = __builtin_nanf("");
-        } else if (tot >= RESC_T) {
+        } else if (tot >= Op::RESC_T) {
             const float k = floorf(__builtin_amdgcn_logf(tot));
             const float alpha = __builtin_amdgcn_exp2f(-k);
             m_run[qt] += k;
@@ -189,8 +186,8 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
         }
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            sc[j & 1] = ATT2_MFMA(kf[j], qf[SQ][j >> 1], sc[j & 1], 0, 0, 0);
-            mfma_acc_agpr(o[PQ][j & 1], vf[j], __builtin_bit_cast(op8, pf[j >> 1]));
+            sc[j & 1] = Op::mfma(kf[j], qf[SQ][j >> 1], sc[j & 1]);
+            mfma_acc_agpr<T>(o[PQ][j & 1], vf[j], __builtin_bit_cast(op8, pf[j >> 1]));
         }
     };
     // vector step: softmax of the score set -> P set, this lane's part of the row sum; fragment refills and one DMA request ride along
@@ -220,7 +217,7 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
                 const float p1 = __builtin_amdgcn_exp2f(sc[bj >> 1][8 * (bj & 1) + e + 1]);
                 lta += p0;
                 ltb += p1;
-                const op2 pk = {(op_t)p0, (op_t)p1};
+                const op2 pk = {(T)p0, (T)p1};
                 pf[bj][e >> 1] = __builtin_bit_cast(unsigned, pk);
             }
             if (c & 1) {   // eight fragment refills spread over the sixteen chunks
@@ -243,8 +240,8 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
         // V_a(t)
         if (pend1) { guard_tripped(1, lsum1); pend1 = 0; }   // PV(1, t-1) has been issued
         lsum0 = v_step(std::integral_constant<int, 0>{}, vb_tag, t);
-        if (!(ABL & 8)) pend0 = __builtin_amdgcn_readfirstlane(__any(!(lsum0 < RESC_T)));
-        vm_wait<3>();   // this wave's K(t+1), V(t+1) have landed; K(t+2), V(t+2), K(t+3) may stay in flight
+        if (!(ABL & 8)) pend0 = __builtin_amdgcn_readfirstlane(__any(!(lsum0 < Op::RESC_T)));
+        dtk_vm_wait<3>();   // this wave's K(t+1), V(t+1) have landed; K(t+2), V(t+2), K(t+3) may stay in flight
         __syncthreads();
         // M_b(t): PV(0, t), S(1, t)
         m_step(std::integral_constant<int, 0>{});
@@ -252,7 +249,7 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
         // V_b(t)
         if (pend0) { guard_tripped(0, lsum0); pend0 = 0; }   // PV(0, t) has been issued
         lsum1 = v_step(std::integral_constant<int, 1>{}, vb_tag, t);
-        if (!(ABL & 8)) pend1 = __builtin_amdgcn_readfirstlane(__any(!(lsum1 < RESC_T)));
+        if (!(ABL & 8)) pend1 = __builtin_amdgcn_readfirstlane(__any(!(lsum1 < Op::RESC_T)));
         __syncthreads();
     };
     if (late) __syncthreads();   // waves 4..7: one step behind
@@ -264,11 +261,11 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
     }
     // PV(1, last)
 #pragma unroll
-    for (int g = 0; g < 8; ++g) mfma_acc_agpr(o[1][g & 1], vf[g], __builtin_bit_cast(op8, pf[g >> 1]));
+    for (int g = 0; g < 8; ++g) mfma_acc_agpr<T>(o[1][g & 1], vf[g], __builtin_bit_cast(op8, pf[g >> 1]));
     if (!late) __syncthreads();  // the early half's extra barrier: both halves have executed the same number
     if (pend1) guard_tripped(1, lsum1);
     agpr_settle();
-    vm_wait<0>();
+    dtk_vm_wait<0>();
     float l_tot[2];
     bool redo = false;
 #pragma unroll
@@ -276,10 +273,10 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
         float a, b;
         halves(l_run[qt], a, b);
         l_tot[qt] = a + b;
-        redo |= __any(!(l_tot[qt] > LOW_T && l_tot[qt] < 0x1p120f));
+        redo |= __any(!(l_tot[qt] > Op::LOW_T && l_tot[qt] < 0x1p120f));
     }
     if (redo && !(ABL & 8)) {
-        safe_pass_impl(Qb, Kb, Vb, O + (size_t)frame * S * D + head * 64, q0, 64, S, Sp, D);   // inlined: see vit_attention2.h
+        safe_pass_impl(Qb, Kb, Vb, O + (size_t)frame * S * D + head * 64, q0, 64, S, Sp, D);   // inlined: see vit_attention_common.h
         return;
     }
 #pragma unroll
@@ -287,18 +284,18 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
         const float inv = 1.f / l_tot[qt];
         const int qi = q0 + qt * 32 + lq;
         if (qi < S) {
-            op_t* orow = O + ((size_t)frame * S + qi) * D + head * 64;
+            T* orow = O + ((size_t)frame * S + qi) * D + head * 64;
 #pragma unroll
             for (int db = 0; db < 2; ++db)
 #pragma unroll
                 for (int pr = 0; pr < 2; ++pr) {
                     typedef unsigned u2v __attribute__((ext_vector_type(2)));
-                    const op4 ve = {(op_t)(o[qt][db][8 * pr + 0] * inv), (op_t)(o[qt][db][8 * pr + 1] * inv),
-                                    (op_t)(o[qt][db][8 * pr + 2] * inv), (op_t)(o[qt][db][8 * pr + 3] * inv)};
-                    const op4 vo = {(op_t)(o[qt][db][8 * pr + 4] * inv), (op_t)(o[qt][db][8 * pr + 5] * inv),
-                                    (op_t)(o[qt][db][8 * pr + 6] * inv), (op_t)(o[qt][db][8 * pr + 7] * inv)};
+                    const op4 ve = {(T)(o[qt][db][8 * pr + 0] * inv), (T)(o[qt][db][8 * pr + 1] * inv),
+                                    (T)(o[qt][db][8 * pr + 2] * inv), (T)(o[qt][db][8 * pr + 3] * inv)};
+                    const op4 vo = {(T)(o[qt][db][8 * pr + 4] * inv), (T)(o[qt][db][8 * pr + 5] * inv),
+                                    (T)(o[qt][db][8 * pr + 6] * inv), (T)(o[qt][db][8 * pr + 7] * inv)};
                     const u2v e = __builtin_bit_cast(u2v, ve), od = __builtin_bit_cast(u2v, vo);
-                    u4v out;
+                    dtk_u4 out;
 #pragma unroll
                     for (int k = 0; k < 2; ++k) {
                         const auto sw = __builtin_amdgcn_permlane32_swap(e[k], od[k], false, false);
@@ -306,10 +303,10 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
                         out[k] = first;
                         out[2 + k] = second;
                     }
-                    *reinterpret_cast<u4v*>(orow + db * 32 + 16 * pr + 8 * hi) = out;
+                    *reinterpret_cast<dtk_u4*>(orow + db * 32 + 16 * pr + 8 * hi) = out;
                 }
         }
     }
 }
 
-}  // namespace ATT2_NS
+}  // namespace attn

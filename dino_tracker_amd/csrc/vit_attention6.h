@@ -1,7 +1,7 @@
 // vit_attention6.h -- flash attention for d_head = 64, fourth generation (round 6): ONE wave per SIMD, 128 queries per wave.
 //
-// Include AFTER vit_attention4.h while the ATT2_* macros are still defined: same per-type namespace, tile layout (K tile + V^T tile of 64
-// keys, 16-byte pieces XOR-swizzled through the DMA's source address), LDS-DMA helpers, fp16 range guards and output layout.
+// Tile layout (K tile + V^T tile of 64 keys, 16-byte pieces XOR-swizzled through the DMA's source address), LDS-DMA, fp16 range
+// guards and output layout are attention4's.
 //
 // Why.  attention4's wave owns two 32-query tiles: a K fragment and a V^T fragment read from LDS serve two tiles --
 // 16 ds_read_b128 and 4 LDS-DMA requests per 32 MFMAs, one barrier per 32 MFMAs; its own ablations price the reads at 5.5 % and the
@@ -28,45 +28,46 @@
 // Arithmetic is attention4's (attention2 MODE 1): optimistic exponentials against a reference estimated once per query, a guard on
 // every tile's row sum, the rescale AFTER the PV product of the tile that tripped it (here: after sub-step u of the next key tile, where
 // PV(u, t) and S(u, t + 1) are issued -- the scores of key tile t + 1 move with the reference), poison and the safe pass.
-#ifndef ATT2_NS
-#error "include vit_attention2.h / vit_attention4.h first and keep ATT2_NS, ATT2_T, ATT2_F16, ATT2_MFMA defined"
-#endif
+#pragma once
+#include "vit_attention_common.h"
 
-namespace ATT2_NS {
+namespace attn {
 
 constexpr int A6_NQ = 4;
 
-inline unsigned attention6_grid(int FH, int S, int* qb_out) {
-    const int QB = (S + 128 * A6_NQ - 1) / (128 * A6_NQ);
-    *qb_out = QB;
-    return (unsigned)(((FH + 7) / 8) * 8 * QB);
-}
-
 // S^T accumulate: A = K fragment (AGPR), B = Q fragment (AGPR), accumulator in VGPRs; the first product of a key block takes the
 // reference as its C operand (-m in all 16 registers of a lane: every accumulator register of a lane belongs to ONE query)
-__device__ __forceinline__ void a6_s_first(f16v& acc, const op8& a, const op8& b, const f16v& c) {
-    if constexpr (F16) asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %3" : "=&v"(acc) : "a"(a), "a"(b), "v"(c));
+template <typename T>
+__device__ __forceinline__ void a6_s_first(f16v& acc, const typename Operand<T>::v8& a, const typename Operand<T>::v8& b,
+                                           const f16v& c) {
+    if constexpr (Operand<T>::F16) asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %3" : "=&v"(acc) : "a"(a), "a"(b), "v"(c));
     else asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %3" : "=&v"(acc) : "a"(a), "a"(b), "v"(c));
 }
-__device__ __forceinline__ void a6_s_next(f16v& acc, const op8& a, const op8& b) {
-    if constexpr (F16) asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(acc) : "a"(a), "a"(b));
+template <typename T>
+__device__ __forceinline__ void a6_s_next(f16v& acc, const typename Operand<T>::v8& a, const typename Operand<T>::v8& b) {
+    if constexpr (Operand<T>::F16) asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(acc) : "a"(a), "a"(b));
     else asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(acc) : "a"(a), "a"(b));
 }
 // O^T accumulate: A = V^T fragment (AGPR), B = P fragment (VGPR), accumulator in AGPRs
-__device__ __forceinline__ void a6_pv(f16v& c, const op8& a, const op8& b) {
-    if constexpr (F16) asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+a"(c) : "a"(a), "v"(b));
+template <typename T>
+__device__ __forceinline__ void a6_pv(f16v& c, const typename Operand<T>::v8& a, const typename Operand<T>::v8& b) {
+    if constexpr (Operand<T>::F16) asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+a"(c) : "a"(a), "v"(b));
     else asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+a"(c) : "a"(a), "v"(b));
 }
 // a fragment from LDS straight into AGPRs (base address in a VGPR + immediate)
-template <int OFF>
-__device__ __forceinline__ void a6_lds_frag(op8& dst, unsigned addr) {
+template <int OFF, typename V8>
+__device__ __forceinline__ void a6_lds_frag(V8& dst, unsigned addr) {
     asm volatile("ds_read_b128 %0, %1 offset:%2" : "=a"(dst) : "v"(addr), "i"(OFF) : "memory");
 }
 
-template <int ABL = 0>
-__global__ __launch_bounds__(256, 1) void attention6_kernel(const op_t* __restrict__ Q, const op_t* __restrict__ Kg,
-                                                            const op_t* __restrict__ Vt, op_t* __restrict__ O, int S, int Sp,
+template <typename T, int ABL = 0>
+__global__ __launch_bounds__(256, 1) void attention6_kernel(const T* __restrict__ Q, const T* __restrict__ Kg,
+                                                            const T* __restrict__ Vt, T* __restrict__ O, int S, int Sp,
                                                             int heads, int D, int FH, int QB) {
+    typedef Operand<T> Op;
+    typedef typename Op::v8 op8;
+    typedef typename Op::v4 op4;
+    typedef typename Op::v2 op2;
     constexpr int NQ = A6_NQ;
     __shared__ __attribute__((aligned(1024))) unsigned char tiles[A4_NB][TILE_BYTES];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -78,10 +79,10 @@ __global__ __launch_bounds__(256, 1) void attention6_kernel(const op_t* __restri
     const int frame = fh / heads, head = fh - frame * heads;
     const int q0 = qb * (128 * NQ) + w * (32 * NQ);
     const int lq = lane & 31, hi = lane >> 5;
-    const op_t* Qb = Q + (size_t)fh * Sp * 64;
-    const op_t* Kb = Kg + (size_t)fh * Sp * 64;
-    const op_t* Vb = Vt + (size_t)fh * 64 * Sp;
-    if (F16) fp16_saturate_mode();
+    const T* Qb = Q + (size_t)fh * Sp * 64;
+    const T* Kb = Kg + (size_t)fh * Sp * 64;
+    const T* Vb = Vt + (size_t)fh * 64 * Sp;
+    if (Op::F16) dtk_fp16_saturate_mode();
 
     // Q^T fragments (B operand) straight into AGPRs: lane (query lq, hi) holds d = 16 ks + 8 hi .. + 7 -- and, in the same trip to
     // memory, the key rows of the reference estimate: keys 0..31, 32..63 and every tile's own 32 keys
@@ -98,7 +99,7 @@ __global__ __launch_bounds__(256, 1) void attention6_kernel(const op_t* __restri
 #pragma unroll
         for (int blk = 0; blk < 2 + NQ; ++blk) {
             const int kr0 = blk < 2 ? blk * 32 : q0 + (blk - 2) * 32;
-            const op_t* kp = Kb + (size_t)min(kr0 + lq, Sp - 1) * 64 + hi * 8;
+            const T* kp = Kb + (size_t)min(kr0 + lq, Sp - 1) * 64 + hi * 8;
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks) kq[blk][ks] = *reinterpret_cast<const op8*>(kp + ks * 16);
         }
@@ -112,15 +113,15 @@ __global__ __launch_bounds__(256, 1) void attention6_kernel(const op_t* __restri
     }
     const unsigned lds_base = (unsigned)(size_t)&tiles[0][0];
     const int ntiles = (S + 63) / 64;
-    const u4v srd_k = make_srd(Kb), srd_v = make_srd(Vb);
+    const dtk_u4 srd_k = dtk_make_srd(Kb), srd_v = dtk_make_srd(Vb);
     unsigned dma_dst[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) dma_dst[i] = __builtin_amdgcn_readfirstlane(lds_base + (i >> 1) * 8192 + (w * 2 + (i & 1)) * 1024);
     auto issue_one = [&](int t, auto buf_tag, int i) {
         constexpr int BUF = decltype(buf_tag)::value;
         const unsigned tt = (unsigned)min(t, ntiles - 1);  // past the end: a harmless repeat keeps the request count per tile uniform
-        if (i < 2) buffer_lds16<BUF * TILE_BYTES>(srd_k, tt * 8192u, kvo[i & 1], dma_dst[i]);
-        else buffer_lds16<BUF * TILE_BYTES>(srd_v, tt * 128u, vvo[i & 1], dma_dst[i]);
+        if (i < 2) dtk_buffer_lds16<BUF * TILE_BYTES>(srd_k, tt * 8192u, kvo[i & 1], dma_dst[i]);
+        else dtk_buffer_lds16<BUF * TILE_BYTES>(srd_v, tt * 128u, vvo[i & 1], dma_dst[i]);
     };
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -152,7 +153,7 @@ __global__ __launch_bounds__(256, 1) void attention6_kernel(const op_t* __restri
                 const int kb = blk < 2 ? blk : 2 + qt;
                 f16v so = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-                for (int ks = 0; ks < 4; ++ks) so = ATT2_MFMA(kq[kb][ks], qf[qt][ks], so, 0, 0, 0);
+                for (int ks = 0; ks < 4; ++ks) so = Op::mfma(kq[kb][ks], qf[qt][ks], so);
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int key = kr0 + (r & 3) + 8 * (r >> 2) + 4 * hi;
@@ -172,7 +173,7 @@ __global__ __launch_bounds__(256, 1) void attention6_kernel(const op_t* __restri
 
     f16v o[NQ][2];   // O^T accumulators (AGPRs): rows d = 32 db + (r & 3) + 8 (r >> 2) + 4 hi, column = query lq
     f16v sc[2][2];   // two score sets [set][key block]: register r of lane-half hi = key 32 b + 16 (r >> 3) + 8 hi + (r & 7)
-    u4v pf[NQ][4];   // P^T fragments [query tile][16-key group]
+    dtk_u4 pf[NQ][4]; // P^T fragments [query tile][16-key group]
     op8 kf[8], vf[8];  // K / V^T fragments (AGPRs)
 #pragma unroll
     for (int qt = 0; qt < NQ; ++qt) {
@@ -194,7 +195,7 @@ __global__ __launch_bounds__(256, 1) void attention6_kernel(const op_t* __restri
 #pragma unroll
     for (int g = 0; g < 8; ++g) {
 #pragma unroll
-        for (int e = 0; e < 8; ++e) vf[g][e] = (op_t)0.f;   // key tile 0 multiplies them with P = 0
+        for (int e = 0; e < 8; ++e) vf[g][e] = (T)0.f;   // key tile 0 multiplies them with P = 0
         asm volatile("" : "+a"(vf[g]));
     }
     // fragment addresses inside a ring buffer: K fragment f = (key block f & 1, d step f >> 1) at ka[f >> 1] + 4096 (f & 1), V^T fragment
@@ -238,9 +239,9 @@ __global__ __launch_bounds__(256, 1) void attention6_kernel(const op_t* __restri
         float a, b;
         halves(lsum, a, b);
         const float tot = a + b;
-        if (!(a < POISON_T && b < POISON_T)) {
+        if (!(a < Op::POISON_T && b < Op::POISON_T)) {
             l_run[qt] = __builtin_nanf("");
-        } else if (tot >= RESC_T) {
+        } else if (tot >= Op::RESC_T) {
             const float k = floorf(__builtin_amdgcn_logf(tot));
             const float alpha = __builtin_amdgcn_exp2f(-k);
             m_run[qt] += k;
@@ -289,7 +290,7 @@ __global__ __launch_bounds__(256, 1) void attention6_kernel(const op_t* __restri
                 asm volatile("v_add_f32 %0, %0, %1" : "+v"(ltb) : "v"(p1));
             }
             unsigned wv;
-            if constexpr (F16) asm volatile("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(wv) : "v"(p0), "v"(p1));
+            if constexpr (Op::F16) asm volatile("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(wv) : "v"(p0), "v"(p1));
             else asm volatile("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(wv) : "v"(p0), "v"(p1));
             pf[SQ][bj][e >> 1] = wv;
         };
@@ -297,10 +298,10 @@ __global__ __launch_bounds__(256, 1) void attention6_kernel(const op_t* __restri
         for (int i = 0; i < 16; ++i) {
             const int j = i >> 1;
             if ((i & 1) == 0) {
-                if (j < 2) a6_s_first(sc[SET][j & 1], kf[j], qf[U][j >> 1], negm[U]);
-                else a6_s_next(sc[SET][j & 1], kf[j], qf[U][j >> 1]);
+                if (j < 2) a6_s_first<T>(sc[SET][j & 1], kf[j], qf[U][j >> 1], negm[U]);
+                else a6_s_next<T>(sc[SET][j & 1], kf[j], qf[U][j >> 1]);
             } else {
-                a6_pv(o[U][j & 1], vf[j], __builtin_bit_cast(op8, pf[U][j >> 1]));
+                a6_pv<T>(o[U][j & 1], vf[j], __builtin_bit_cast(op8, pf[U][j >> 1]));
             }
             if (!(ABL & 128) && REFILL) {   // the register's last use was the MFMA just issued
                 if (i & 1) {
@@ -337,10 +338,10 @@ __global__ __launch_bounds__(256, 1) void attention6_kernel(const op_t* __restri
         }
         // tile SQ: the guard on the row sums just formed (handled after ITS next PV product, i.e. after sub-step SQ of the next key tile)
         lsum[SQ] = lt;
-        pend[SQ] = __builtin_amdgcn_ballot_w64(!(lt < RESC_T)) != 0ull;   // (a compare into VCC and one scalar test)
+        pend[SQ] = __builtin_amdgcn_ballot_w64(!(lt < Op::RESC_T)) != 0ull;   // (a compare into VCC and one scalar test)
     };
     auto key_tile = [&](auto vb_tag, int t) {
-        vm_wait<4>();   // this wave's requests of tile t + 1 have landed (those of tile t + 2 stay in flight)
+        dtk_vm_wait<4>();   // this wave's requests of tile t + 1 have landed (those of tile t + 2 stay in flight)
         // The fragment reads of the previous key tile's last sub-step are asm statements: not the compiler's to wait for.  They were
         // issued one per slot in the order kf[0], vf[0], kf[1], ... and LDS operations return in order: the first eight (kf[0..3],
         // vf[0..3], issued 9 .. 16 slots ago) cover slots 0 .. 7 of sub-step 0; the other eight are waited for in its slot 7.
@@ -368,29 +369,29 @@ __global__ __launch_bounds__(256, 1) void attention6_kernel(const op_t* __restri
             const int bj = c >> 2, e = 2 * (c & 3);
             const float p0 = __builtin_amdgcn_exp2f(sc[1][bj >> 1][8 * (bj & 1) + e]), p1 = __builtin_amdgcn_exp2f(sc[1][bj >> 1][8 * (bj & 1) + e + 1]);
             lta += p0 + p1;
-            const op2 pk = {(op_t)p0, (op_t)p1};
+            const op2 pk = {(T)p0, (T)p1};
             pf[NQ - 1][bj][e >> 1] = __builtin_bit_cast(unsigned, pk);
         }
         l_run[NQ - 1] += lta;
         lsum[NQ - 1] = lta;
-        pend[NQ - 1] = (ABL & 8) ? 0 : (__builtin_amdgcn_ballot_w64(!(lta < RESC_T)) != 0ull);
+        pend[NQ - 1] = (ABL & 8) ? 0 : (__builtin_amdgcn_ballot_w64(!(lta < Op::RESC_T)) != 0ull);
         // (the converts above are compiler-scheduled VALU writes of registers an asm MFMA reads next: keep them apart)
         asm volatile("s_nop 4" ::: "memory");
 #pragma unroll
-        for (int g = 0; g < 8; ++g) a6_pv(o[0][g & 1], vf[g], __builtin_bit_cast(op8, pf[0][g >> 1]));
+        for (int g = 0; g < 8; ++g) a6_pv<T>(o[0][g & 1], vf[g], __builtin_bit_cast(op8, pf[0][g >> 1]));
 #pragma unroll
-        for (int g = 0; g < 8; ++g) a6_pv(o[1][g & 1], vf[g], __builtin_bit_cast(op8, pf[1][g >> 1]));
+        for (int g = 0; g < 8; ++g) a6_pv<T>(o[1][g & 1], vf[g], __builtin_bit_cast(op8, pf[1][g >> 1]));
 #pragma unroll
-        for (int g = 0; g < 8; ++g) a6_pv(o[2][g & 1], vf[g], __builtin_bit_cast(op8, pf[2][g >> 1]));
+        for (int g = 0; g < 8; ++g) a6_pv<T>(o[2][g & 1], vf[g], __builtin_bit_cast(op8, pf[2][g >> 1]));
 #pragma unroll
-        for (int g = 0; g < 8; ++g) a6_pv(o[3][g & 1], vf[g], __builtin_bit_cast(op8, pf[3][g >> 1]));
+        for (int g = 0; g < 8; ++g) a6_pv<T>(o[3][g & 1], vf[g], __builtin_bit_cast(op8, pf[3][g >> 1]));
     }
     if (pend[0]) guard_tripped(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{}, lsum[0], false);
     if (pend[1]) guard_tripped(std::integral_constant<int, 1>{}, std::integral_constant<int, 0>{}, lsum[1], false);
     if (pend[2]) guard_tripped(std::integral_constant<int, 2>{}, std::integral_constant<int, 0>{}, lsum[2], false);
     if (pend[3]) guard_tripped(std::integral_constant<int, 3>{}, std::integral_constant<int, 0>{}, lsum[3], false);
     agpr_settle();
-    vm_wait<0>();
+    dtk_vm_wait<0>();
     float l_tot[NQ];
     bool redo = false;
 #pragma unroll
@@ -398,10 +399,10 @@ __global__ __launch_bounds__(256, 1) void attention6_kernel(const op_t* __restri
         float a, b;
         halves(l_run[qt], a, b);
         l_tot[qt] = a + b;
-        redo |= __any(!(l_tot[qt] > LOW_T && l_tot[qt] < 0x1p120f));
+        redo |= __any(!(l_tot[qt] > Op::LOW_T && l_tot[qt] < 0x1p120f));
     }
     if (redo && !(ABL & 8)) {
-        safe_pass<6>(Qb, Kb, Vb, O + (size_t)frame * S * D + head * 64, q0, 32 * NQ, S, Sp, D);
+        safe_pass<T, 6>(Qb, Kb, Vb, O + (size_t)frame * S * D + head * 64, q0, 32 * NQ, S, Sp, D);
         return;
     }
 #pragma unroll
@@ -409,19 +410,19 @@ __global__ __launch_bounds__(256, 1) void attention6_kernel(const op_t* __restri
         const float inv = 1.f / l_tot[qt];
         const int qi = q0 + qt * 32 + lq;
         if (qi < S) {
-            op_t* orow = O + ((size_t)frame * S + qi) * D + head * 64;
+            T* orow = O + ((size_t)frame * S + qi) * D + head * 64;
             // (attention4's store: the two halves of a query trade 8-byte pieces by v_permlane32_swap, 16-byte stores)
 #pragma unroll
             for (int db = 0; db < 2; ++db)
 #pragma unroll
                 for (int pr = 0; pr < 2; ++pr) {
                     typedef unsigned u2v __attribute__((ext_vector_type(2)));
-                    const op4 ve = {(op_t)(o[qt][db][8 * pr + 0] * inv), (op_t)(o[qt][db][8 * pr + 1] * inv),
-                                    (op_t)(o[qt][db][8 * pr + 2] * inv), (op_t)(o[qt][db][8 * pr + 3] * inv)};
-                    const op4 vo = {(op_t)(o[qt][db][8 * pr + 4] * inv), (op_t)(o[qt][db][8 * pr + 5] * inv),
-                                    (op_t)(o[qt][db][8 * pr + 6] * inv), (op_t)(o[qt][db][8 * pr + 7] * inv)};
+                    const op4 ve = {(T)(o[qt][db][8 * pr + 0] * inv), (T)(o[qt][db][8 * pr + 1] * inv),
+                                    (T)(o[qt][db][8 * pr + 2] * inv), (T)(o[qt][db][8 * pr + 3] * inv)};
+                    const op4 vo = {(T)(o[qt][db][8 * pr + 4] * inv), (T)(o[qt][db][8 * pr + 5] * inv),
+                                    (T)(o[qt][db][8 * pr + 6] * inv), (T)(o[qt][db][8 * pr + 7] * inv)};
                     const u2v e = __builtin_bit_cast(u2v, ve), od = __builtin_bit_cast(u2v, vo);
-                    u4v out;
+                    dtk_u4 out;
 #pragma unroll
                     for (int k = 0; k < 2; ++k) {
                         const auto sw = __builtin_amdgcn_permlane32_swap(e[k], od[k], false, false);
@@ -430,10 +431,10 @@ __global__ __launch_bounds__(256, 1) void attention6_kernel(const op_t* __restri
                         out[2 + k] = second;
                     }
                     const int d = db * 32 + 16 * pr + 8 * hi;
-                    *reinterpret_cast<u4v*>(orow + d) = out;
+                    *reinterpret_cast<dtk_u4*>(orow + d) = out;
                 }
         }
     }
 }
 
-}  // namespace ATT2_NS
+}  // namespace attn

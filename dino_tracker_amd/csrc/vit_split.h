@@ -346,7 +346,7 @@ __global__ __launch_bounds__(512, 1) void gemm_split_dma_kernel(const T* __restr
     const unsigned b_off = 2 * SD_M * 64 + ((wc * 64 + fj) * 4 + (fg ^ fsw)) * 16;
     issue(0, 0);
     issue(1, 1);
-    ws_wait<SD_REQ>();   // stage 0 landed (stage 1 may still fly)
+    dtk_vm_wait<SD_REQ>();   // stage 0 landed (stage 1 may still fly)
     __syncthreads();
     int buf = 0;
     for (int ks = 0; ks < nk; ++ks) {
@@ -369,11 +369,11 @@ __global__ __launch_bounds__(512, 1) void gemm_split_dma_kernel(const T* __restr
                 acc[mi][ni] = mfma16(bh, ah[mi], acc[mi][ni]);
             }
         }
-        ws_wait<SD_REQ>();   // stage ks + 1 landed; the requests of ks + 2 stay in flight
+        dtk_vm_wait<SD_REQ>();   // stage ks + 1 landed; the requests of ks + 2 stay in flight
         __syncthreads();
         buf = buf == 2 ? 0 : buf + 1;
     }
-    ws_wait<0>();
+    dtk_vm_wait<0>();
     float amax = 0.f;
     typedef typename Vec<T>::t4 T4;
     // Round 6: the epilogues leave through LDS as whole rows (vit.hip, gemm_wide_kernel: one workgroup per CU, nothing overlaps the

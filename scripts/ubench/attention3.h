@@ -1,7 +1,9 @@
 // attention3.h -- round-3 experiment (NEGATIVE, kept for the micro-benchmark only; not part of libdtk.so).
-// Include AFTER vit_attention2.h while its ATT2_* macros are still defined (it re-opens the same namespace and reuses the
-// tile layout, the guards and the safe pass).
-namespace ATT2_NS {
+// It reuses attention2's tile layout, guards and safe pass (vit_attention_common.h).
+#pragma once
+#include "vit_attention_common.h"
+
+namespace attn {
 // ---------------------------------------------------------------------------------------------------------------------
 // attention3_kernel (round 3): the same tiles, layouts, guards and safe pass, but SOFTWARE-PIPELINED ACROSS KEY TILES inside
 // each wave.  Round 2's SQ counters say why the kernel above stops at 0.43 of the MFMA peak: per launch a SIMD spends 2.9 M
@@ -15,12 +17,13 @@ namespace ATT2_NS {
 // 256-thread ones) and a deeper LDS ring (K of tile t+1 and V^T of tile t are live at once; NB buffers, NB - 2 tiles in
 // flight).  MODE 1 arithmetic only.  NW = waves per workgroup (8 or 4), 32 queries per wave.
 // ---------------------------------------------------------------------------------------------------------------------
-template <int NW, int NB, int ABL = 0>
-__global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void attention3_kernel(const op_t* __restrict__ Q,
-                                                                              const op_t* __restrict__ Kg,
-                                                                              const op_t* __restrict__ Vt,
-                                                                              op_t* __restrict__ O, int S, int Sp, int heads,
-                                                                              int D, int FH, int QB) {
+template <typename T, int NW, int NB, int ABL = 0>
+__global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void attention3_kernel(const T* __restrict__ Q, const T* __restrict__ Kg,
+                                                                              const T* __restrict__ Vt, T* __restrict__ O, int S,
+                                                                              int Sp, int heads, int D, int FH, int QB) {
+    typedef Operand<T> Op;
+    typedef typename Op::v8 op8;
+    typedef typename Op::v4 op4;
     __shared__ __attribute__((aligned(1024))) unsigned char tiles[NB][TILE_BYTES];
     constexpr int RPW = 8 / NW;  // DMA requests per wave for the K part of a tile (and as many for the V^T part)
     const int tid = threadIdx.x, lane = tid & 63;
@@ -32,13 +35,13 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void attention3_kernel(co
     const int frame = fh / heads, head = fh - frame * heads;
     const int q0 = qb * (32 * NW) + w * 32;
     const int lq = lane & 31, hi = lane >> 5;
-    const op_t* Qb = Q + (size_t)fh * Sp * 64;
-    const op_t* Kb = Kg + (size_t)fh * Sp * 64;
-    const op_t* Vb = Vt + (size_t)fh * 64 * Sp;
-    if (F16) fp16_saturate_mode();
+    const T* Qb = Q + (size_t)fh * Sp * 64;
+    const T* Kb = Kg + (size_t)fh * Sp * 64;
+    const T* Vb = Vt + (size_t)fh * 64 * Sp;
+    if (Op::F16) dtk_fp16_saturate_mode();
 
-    const op_t* ksrc[RPW];
-    const op_t* vsrc[RPW];
+    const T* ksrc[RPW];
+    const T* vsrc[RPW];
 #pragma unroll
     for (int r = 0; r < RPW; ++r) {
         const int lrow = (w * RPW + r) * 8 + (lane >> 3), lpc = (lane & 7) ^ ((lrow >> 1) & 7);
@@ -51,9 +54,9 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void attention3_kernel(co
         const int tt = min(t, ntiles - 1);  // past the end: a harmless repeat keeps the request count per tile uniform
 #pragma unroll
         for (int r = 0; r < RPW; ++r) {
-            glds16(ksrc[r] + (size_t)tt * 64 * 64,
+            dtk_glds16(ksrc[r] + (size_t)tt * 64 * 64,
                    __builtin_amdgcn_readfirstlane(lds_base + buf * TILE_BYTES + (w * RPW + r) * 1024));
-            glds16(vsrc[r] + (size_t)tt * 64,
+            dtk_glds16(vsrc[r] + (size_t)tt * 64,
                    __builtin_amdgcn_readfirstlane(lds_base + buf * TILE_BYTES + 8192 + (w * RPW + r) * 1024));
         }
     };
@@ -89,13 +92,13 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void attention3_kernel(co
 #pragma unroll
         for (int blk = 0; blk < 3; ++blk) {
             const int kr0 = blk < 2 ? blk * 32 : q0;
-            const op_t* kp = Kb + (size_t)min(kr0 + lq, Sp - 1) * 64 + hi * 8;
+            const T* kp = Kb + (size_t)min(kr0 + lq, Sp - 1) * 64 + hi * 8;
             op8 kf[4];
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks) kf[ks] = *reinterpret_cast<const op8*>(kp + ks * 16);
             f16v so = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-            for (int ks = 0; ks < 4; ++ks) so = ATT2_MFMA(kf[ks], qf[ks], so, 0, 0, 0);
+            for (int ks = 0; ks < 4; ++ks) so = Op::mfma(kf[ks], qf[ks], so);
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int key = kr0 + (r & 3) + 8 * (r >> 2) + 4 * hi;
@@ -110,7 +113,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void attention3_kernel(co
             m_run = est;
         }
     }
-    vm_wait<0>();  // the first NB - 1 tiles have landed
+    dtk_vm_wait<0>();  // the first NB - 1 tiles have landed
     __syncthreads();
 
     const f16v zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -129,7 +132,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void attention3_kernel(co
 #pragma unroll
         for (int f = 0; f < 8; ++f) {
             const op8 kr = *reinterpret_cast<const op8*>(tk + (koff[f & 1] ^ ((f >> 1) << 5)));
-            scA[f & 1] = ATT2_MFMA(kr, qf[f >> 1], f < 2 ? zero16 : scA[f & 1], 0, 0, 0);
+            scA[f & 1] = Op::mfma(kr, qf[f >> 1], f < 2 ? zero16 : scA[f & 1]);
         }
         if (ntiles == 1 && (S & 63) != 0) mask_tail(scA, 0);
     }
@@ -153,8 +156,8 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void attention3_kernel(co
             if (SUB) sv += nm;
             const f2 p = (ABL & 1) ? sv * f2{0.01f, 0.01f} : f2{__builtin_amdgcn_exp2f(sv[0]), __builtin_amdgcn_exp2f(sv[1])};
             lt += p;
-            pf[bj][e] = (op_t)p[0];
-            pf[bj][e + 1] = (op_t)p[1];
+            pf[bj][e] = (T)p[0];
+            pf[bj][e + 1] = (T)p[1];
         };
         // MFMA of slot i (issued in front of VALU chunk i):   Q0 Q1 Q2 Q3 | P0 Q4 P1 Q5 | P2 Q6 P3 Q7 | P4 P5 - - | tail P6 P7
         // (Qf = K fragment f of the NEXT tile; Pg = V^T fragment g of THIS tile, g = 2 bj + d-block: needs P group bj = chunks
@@ -163,11 +166,11 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void attention3_kernel(co
         vr[0] = ldv(0); vr[1] = ldv(1);
         auto qk = [&](int f) {
             if (f + 3 < 8) kr[(f + 3) & 3] = ldk(f + 3);
-            nxt[f & 1] = ATT2_MFMA(kr[f & 3], qf[f >> 1], f < 2 ? zero16 : nxt[f & 1], 0, 0, 0);
+            nxt[f & 1] = Op::mfma(kr[f & 3], qf[f >> 1], f < 2 ? zero16 : nxt[f & 1]);
         };
         auto pv = [&](int g) {
             if (g + 2 < 8) vr[(g + 2) & 3] = ldv(g + 2);
-            o[g & 1] = ATT2_MFMA(vr[g & 3], pf[g >> 1], o[g & 1], 0, 0, 0);
+            o[g & 1] = Op::mfma(vr[g & 3], pf[g >> 1], o[g & 1]);
         };
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
@@ -183,16 +186,16 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void attention3_kernel(co
         __builtin_amdgcn_sched_barrier(0);
         const float lsum = lt[0] + lt[1];
         l_run += lt;
-        const bool resc = !(ABL & 8) && __builtin_amdgcn_readfirstlane(__any(!(lsum < RESC_T)));
+        const bool resc = !(ABL & 8) && __builtin_amdgcn_readfirstlane(__any(!(lsum < Op::RESC_T)));
         if (t + 1 == ntiles - 1 && (S & 63) != 0) mask_tail(nxt, t + 1);
         if (resc) {
             asm volatile("; guard tripped" ::: "memory");
             float a, b;
             halves(lsum, a, b);
             const float tot = a + b;
-            if (!(a < POISON_T && b < POISON_T)) {
+            if (!(a < Op::POISON_T && b < Op::POISON_T)) {
                 l_run = f2{__builtin_nanf(""), __builtin_nanf("")};
-            } else if (tot >= RESC_T) {
+            } else if (tot >= Op::RESC_T) {
                 const float k = floorf(__builtin_amdgcn_logf(tot));
                 const float alpha = __builtin_amdgcn_exp2f(-k);
                 // the scores of the NEXT tile are raw (the reference is subtracted when they are exponentiated): only O, l move
@@ -205,7 +208,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void attention3_kernel(co
                 has_m = true;
             }
         }
-        vm_wait<2 * RPW * (NB - 3)>();  // tile t+2 has landed (K read by the next iteration); t+3 .. stay in flight
+        dtk_vm_wait<2 * RPW * (NB - 3)>();  // tile t+2 has landed (K read by the next iteration); t+3 .. stay in flight
         if (!(ABL & 16)) __syncthreads();
         vbuf = kbuf;
     };
@@ -219,29 +222,29 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void attention3_kernel(co
     if (t < ntiles) {
         if (has_m) body(scA, scB, t, std::true_type{}); else body(scA, scB, t, std::false_type{});
     }
-    vm_wait<0>();
+    dtk_vm_wait<0>();
     const float l_half = l_run[0] + l_run[1];
     float la, lb;
     halves(l_half, la, lb);
     const float l_tot = la + lb;
-    if (!(ABL & 8) && __any(!(l_tot > LOW_T && l_tot < 0x1p120f))) {
-        safe_pass<3>(Qb, Kb, Vb, O + (size_t)frame * S * D + head * 64, q0, 32, S, Sp, D);
+    if (!(ABL & 8) && __any(!(l_tot > Op::LOW_T && l_tot < 0x1p120f))) {
+        safe_pass<T, 3>(Qb, Kb, Vb, O + (size_t)frame * S * D + head * 64, q0, 32, S, Sp, D);
         return;
     }
     const float inv = 1.f / l_tot;
     const int qi = q0 + lq;
     if (qi < S) {
-        op_t* orow = O + ((size_t)frame * S + qi) * D + head * 64;
+        T* orow = O + ((size_t)frame * S + qi) * D + head * 64;
 #pragma unroll
         for (int db = 0; db < 2; ++db)
 #pragma unroll
             for (int rq = 0; rq < 4; ++rq) {
                 const int d = db * 32 + 8 * rq + 4 * hi;
-                op4 v = {(op_t)(o[db][4 * rq + 0] * inv), (op_t)(o[db][4 * rq + 1] * inv),
-                         (op_t)(o[db][4 * rq + 2] * inv), (op_t)(o[db][4 * rq + 3] * inv)};
+                op4 v = {(T)(o[db][4 * rq + 0] * inv), (T)(o[db][4 * rq + 1] * inv),
+                         (T)(o[db][4 * rq + 2] * inv), (T)(o[db][4 * rq + 3] * inv)};
                 *reinterpret_cast<op4*>(orow + d) = v;
             }
     }
 }
 
-}  // namespace ATT2_NS
+}  // namespace attn

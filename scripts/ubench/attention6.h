@@ -1,6 +1,6 @@
 // attention6.h -- EXPERIMENT (round 6): attention4's structure with NQ query tiles per wave instead of two.
 //
-// Include after vit_attention4.h while the ATT2_* macros are defined (same per-type namespace, tile layout and DMA helpers).
+// Tile layout, DMA and helpers are attention4's (vit_attention_common.h).
 //
 // attention4: one wave per SIMD, 64 queries per wave; a K fragment and a V^T fragment are read from LDS once per key tile and serve two
 // 32-query tiles: 16 ds_read_b128 and 4 LDS-DMA requests per 32 MFMAs.  Its own ablations price the LDS reads at 5.5 % and the DMA at 6 %
@@ -20,23 +20,19 @@
 //
 // THIS FILE MEASURES THE SCHEDULE ONLY: no reference estimate, no guards, no safe pass (scores enter the exponential as they are;
 // fine for the benchmark's random operands, wrong for the harness's stress rows).  If it pays, the guards of attention4 move in.
-#ifndef ATT2_NS
-#error "include vit_attention2.h / vit_attention4.h first and keep ATT2_NS, ATT2_T, ATT2_F16, ATT2_MFMA defined"
-#endif
+#pragma once
+#include "vit_attention_common.h"
 
-namespace ATT2_NS {
+namespace attn {
 
-template <int NQ>
-inline unsigned attention6_grid(int FH, int S, int* qb_out) {
-    const int QB = (S + 128 * NQ - 1) / (128 * NQ);
-    *qb_out = QB;
-    return (unsigned)(((FH + 7) / 8) * 8 * QB);
-}
-
-template <int NQ, int ABL = 0>
-__global__ __launch_bounds__(256, 1) void attention6_kernel(const op_t* __restrict__ Q, const op_t* __restrict__ Kg,
-                                                            const op_t* __restrict__ Vt, op_t* __restrict__ O, int S, int Sp,
+template <typename T, int NQ, int ABL = 0>
+__global__ __launch_bounds__(256, 1) void attention6_kernel(const T* __restrict__ Q, const T* __restrict__ Kg,
+                                                            const T* __restrict__ Vt, T* __restrict__ O, int S, int Sp,
                                                             int heads, int D, int FH, int QB) {
+    typedef Operand<T> Op;
+    typedef typename Op::v8 op8;
+    typedef typename Op::v4 op4;
+    typedef typename Op::v2 op2;
     __shared__ __attribute__((aligned(1024))) unsigned char tiles[A4_NB][TILE_BYTES];
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -47,10 +43,10 @@ __global__ __launch_bounds__(256, 1) void attention6_kernel(const op_t* __restri
     const int frame = fh / heads, head = fh - frame * heads;
     const int q0 = qb * (128 * NQ) + w * (32 * NQ);
     const int lq = lane & 31, hi = lane >> 5;
-    const op_t* Qb = Q + (size_t)fh * Sp * 64;
-    const op_t* Kb = Kg + (size_t)fh * Sp * 64;
-    const op_t* Vb = Vt + (size_t)fh * 64 * Sp;
-    if (F16) fp16_saturate_mode();
+    const T* Qb = Q + (size_t)fh * Sp * 64;
+    const T* Kb = Kg + (size_t)fh * Sp * 64;
+    const T* Vb = Vt + (size_t)fh * 64 * Sp;
+    if (Op::F16) dtk_fp16_saturate_mode();
 
     // Q^T fragments (B operand) straight into AGPRs: lane (query lq, hi) holds d = 16 ks + 8 hi .. + 7
     op8 qf[NQ][4];
@@ -76,15 +72,15 @@ __global__ __launch_bounds__(256, 1) void attention6_kernel(const op_t* __restri
     }
     const unsigned lds_base = (unsigned)(size_t)&tiles[0][0];
     const int ntiles = (S + 63) / 64;
-    const u4v srd_k = make_srd(Kb), srd_v = make_srd(Vb);
+    const dtk_u4 srd_k = dtk_make_srd(Kb), srd_v = dtk_make_srd(Vb);
     unsigned dma_dst[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) dma_dst[i] = __builtin_amdgcn_readfirstlane(lds_base + (i >> 1) * 8192 + (w * 2 + (i & 1)) * 1024);
     auto issue_one = [&](int t, auto buf_tag, int i) {
         constexpr int BUF = decltype(buf_tag)::value;
         const unsigned tt = (unsigned)min(t, ntiles - 1);
-        if (i < 2) buffer_lds16<BUF * TILE_BYTES>(srd_k, tt * 8192u, kvo[i & 1], dma_dst[i]);
-        else buffer_lds16<BUF * TILE_BYTES>(srd_v, tt * 128u, vvo[i & 1], dma_dst[i]);
+        if (i < 2) dtk_buffer_lds16<BUF * TILE_BYTES>(srd_k, tt * 8192u, kvo[i & 1], dma_dst[i]);
+        else dtk_buffer_lds16<BUF * TILE_BYTES>(srd_v, tt * 128u, vvo[i & 1], dma_dst[i]);
     };
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -95,7 +91,7 @@ __global__ __launch_bounds__(256, 1) void attention6_kernel(const op_t* __restri
 
     f16v o[NQ][2];   // O^T accumulators (AGPRs)
     f16v sc[2][2];   // two score sets, [set][key block]
-    u4v pf[NQ][4];   // P^T fragments [query tile][16-key group]
+    dtk_u4 pf[NQ][4]; // P^T fragments [query tile][16-key group]
     op8 kf[8], vf[8];
     float l_run[NQ];
 #pragma unroll
@@ -130,8 +126,8 @@ __global__ __launch_bounds__(256, 1) void attention6_kernel(const op_t* __restri
 #pragma unroll
     for (int g = 0; g < 8; ++g)
 #pragma unroll
-        for (int e = 0; e < 8; ++e) vf[g][e] = (op_t)0.f;
-    vm_wait<0>();
+        for (int e = 0; e < 8; ++e) vf[g][e] = (T)0.f;
+    dtk_vm_wait<0>();
     __syncthreads();
 
 #pragma clang diagnostic push
@@ -181,12 +177,12 @@ __global__ __launch_bounds__(256, 1) void attention6_kernel(const op_t* __restri
             asm volatile("v_add_f32 %0, %0, %1" : "+v"(lta) : "v"(p0));
             asm volatile("v_add_f32 %0, %0, %1" : "+v"(ltb) : "v"(p1));
             unsigned wv;
-            if constexpr (F16) asm volatile("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(wv) : "v"(p0), "v"(p1));
+            if constexpr (Op::F16) asm volatile("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(wv) : "v"(p0), "v"(p1));
             else asm volatile("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(wv) : "v"(p0), "v"(p1));
             pf[SQ][bj][e >> 1] = wv;
         };
         auto s_mfma = [&](f16v& acc, op8 a, op8 b, bool first) {
-            if constexpr (F16) {
+            if constexpr (Op::F16) {
                 if (first) asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, 0" : "=&v"(acc) : "v"(a), "a"(b));
                 else asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "a"(b));
             } else {
@@ -198,7 +194,7 @@ __global__ __launch_bounds__(256, 1) void attention6_kernel(const op_t* __restri
         for (int i = 0; i < 16; ++i) {
             const int j = i >> 1;
             if ((i & 1) == 0) s_mfma(sc[SET][j & 1], kf[j], qf[U][j >> 1], j < 2);
-            else mfma_acc_agpr(o[U][j & 1], vf[j], __builtin_bit_cast(op8, pf[U][j >> 1]));
+            else mfma_acc_agpr<T>(o[U][j & 1], vf[j], __builtin_bit_cast(op8, pf[U][j >> 1]));
             if (!(ABL & 128) && REFILL) {
                 if (i & 1) vf[j] = ldv(VB, j);
                 else kf[j] = ldk(KB, j);
@@ -219,7 +215,7 @@ __global__ __launch_bounds__(256, 1) void attention6_kernel(const op_t* __restri
     // one key tile: NQ sub-steps; the score set of sub-step u is (PAR0 + u) & 1
     auto key_tile = [&](auto vb_tag, auto par_tag, int t) {
         constexpr int PAR0 = decltype(par_tag)::value;
-        vm_wait<4>();
+        dtk_vm_wait<4>();
         if (!(ABL & 16)) __syncthreads();
         sub_step(std::integral_constant<int, 0>{}, vb_tag, std::integral_constant<int, PAR0 & 1>{}, t);
         sub_step(std::integral_constant<int, 1>{}, vb_tag, std::integral_constant<int, (PAR0 + 1) & 1>{}, t);
@@ -245,17 +241,17 @@ __global__ __launch_bounds__(256, 1) void attention6_kernel(const op_t* __restri
             const float s1 = last_set ? sc[1][bj >> 1][8 * (bj & 1) + e + 1] : sc[0][bj >> 1][8 * (bj & 1) + e + 1];
             const float p0 = __builtin_amdgcn_exp2f(s0), p1 = __builtin_amdgcn_exp2f(s1);
             lta += p0 + p1;
-            const op2 pk = {(op_t)p0, (op_t)p1};
+            const op2 pk = {(T)p0, (T)p1};
             pf[NQ - 1][bj][e >> 1] = __builtin_bit_cast(unsigned, pk);
         }
         l_run[NQ - 1] += lta;
 #pragma unroll
         for (int qt = 0; qt < NQ; ++qt)
 #pragma unroll
-            for (int g = 0; g < 8; ++g) mfma_acc_agpr(o[qt][g & 1], vf[g], __builtin_bit_cast(op8, pf[qt][g >> 1]));
+            for (int g = 0; g < 8; ++g) mfma_acc_agpr<T>(o[qt][g & 1], vf[g], __builtin_bit_cast(op8, pf[qt][g >> 1]));
     }
     agpr_settle();
-    vm_wait<0>();
+    dtk_vm_wait<0>();
 #pragma unroll
     for (int qt = 0; qt < NQ; ++qt) {
         float a, b;
@@ -263,18 +259,18 @@ __global__ __launch_bounds__(256, 1) void attention6_kernel(const op_t* __restri
         const float inv = 1.f / (a + b);
         const int qi = q0 + qt * 32 + lq;
         if (qi < S) {
-            op_t* orow = O + ((size_t)frame * S + qi) * D + head * 64;
+            T* orow = O + ((size_t)frame * S + qi) * D + head * 64;
 #pragma unroll
             for (int db = 0; db < 2; ++db)
 #pragma unroll
                 for (int pr = 0; pr < 2; ++pr) {
                     typedef unsigned u2v __attribute__((ext_vector_type(2)));
-                    const op4 ve = {(op_t)(o[qt][db][8 * pr + 0] * inv), (op_t)(o[qt][db][8 * pr + 1] * inv),
-                                    (op_t)(o[qt][db][8 * pr + 2] * inv), (op_t)(o[qt][db][8 * pr + 3] * inv)};
-                    const op4 vo = {(op_t)(o[qt][db][8 * pr + 4] * inv), (op_t)(o[qt][db][8 * pr + 5] * inv),
-                                    (op_t)(o[qt][db][8 * pr + 6] * inv), (op_t)(o[qt][db][8 * pr + 7] * inv)};
+                    const op4 ve = {(T)(o[qt][db][8 * pr + 0] * inv), (T)(o[qt][db][8 * pr + 1] * inv),
+                                    (T)(o[qt][db][8 * pr + 2] * inv), (T)(o[qt][db][8 * pr + 3] * inv)};
+                    const op4 vo = {(T)(o[qt][db][8 * pr + 4] * inv), (T)(o[qt][db][8 * pr + 5] * inv),
+                                    (T)(o[qt][db][8 * pr + 6] * inv), (T)(o[qt][db][8 * pr + 7] * inv)};
                     const u2v e = __builtin_bit_cast(u2v, ve), od = __builtin_bit_cast(u2v, vo);
-                    u4v out;
+                    dtk_u4 out;
 #pragma unroll
                     for (int k = 0; k < 2; ++k) {
                         const auto sw = __builtin_amdgcn_permlane32_swap(e[k], od[k], false, false);
@@ -283,10 +279,10 @@ __global__ __launch_bounds__(256, 1) void attention6_kernel(const op_t* __restri
                         out[2 + k] = second;
                     }
                     const int d = db * 32 + 16 * pr + 8 * hi;
-                    *reinterpret_cast<u4v*>(orow + d) = out;
+                    *reinterpret_cast<dtk_u4*>(orow + d) = out;
                 }
         }
     }
 }
 
-}  // namespace ATT2_NS
+}  // namespace attn

@@ -14,34 +14,12 @@
 #include <type_traits>
 #include <vector>
 
-#define ATT2_NS att2_f16
-#define ATT2_T _Float16
-#define ATT2_F16 1
-#define ATT2_MFMA __builtin_amdgcn_mfma_f32_32x32x16_f16
 #include "vit_attention2.h"
 #ifndef ATTN_NO_V3
 #include "attention3.h"
 #endif
 #include "vit_attention4.h"
 #include "attention6.h"
-#undef ATT2_NS
-#undef ATT2_T
-#undef ATT2_F16
-#undef ATT2_MFMA
-#define ATT2_NS att2_bf16
-#define ATT2_T __bf16
-#define ATT2_F16 0
-#define ATT2_MFMA __builtin_amdgcn_mfma_f32_32x32x16_bf16
-#include "vit_attention2.h"
-#ifndef ATTN_NO_V3
-#include "attention3.h"
-#endif
-#include "vit_attention4.h"
-#include "attention6.h"
-#undef ATT2_NS
-#undef ATT2_T
-#undef ATT2_F16
-#undef ATT2_MFMA
 
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "%s: %s\n", #x, hipGetErrorString(e_)); exit(1); } } while (0)
 
@@ -144,38 +122,37 @@ struct Run {
             check(name);
         };
         printf("== %s operands: %d frames x %d heads, S = %d (Sp %d), %.2f TFLOP per launch\n", F16 ? "fp16" : "bf16", F, heads, S, Sp, flop * 1e-12);
-        using namespace att2c;
-#define NSK(x) std::conditional<F16, std::true_type, std::false_type>::type::value ? 0 : 0
-        auto v2 = [&](auto kern, int QT) { int QB; const unsigned g = attention2_grid(FH, S, QT, &QB);
+        using namespace attn;
+        auto v2 = [&](auto kern, int QT) { int QB; const unsigned g = attention_grid(FH, S, 256 * QT, &QB);
             hipLaunchKernelGGL(kern, dim3(g), dim3(512), 0, 0, (const T*)q, (const T*)k, (const T*)vt, o2, S, Sp, heads, D, FH, QB); };
         auto v3 = [&](auto kern, int NW) { const int QB = (S + 32 * NW - 1) / (32 * NW); const unsigned g = (unsigned)(((FH + 7) / 8) * 8 * QB);
             hipLaunchKernelGGL(kern, dim3(g), dim3(64 * NW), 0, 0, (const T*)q, (const T*)k, (const T*)vt, o2, S, Sp, heads, D, FH, QB); };
-        auto v4 = [&](auto kern) { int QB; const unsigned g = att2_f16::attention4_grid(FH, S, &QB);
+        auto v4 = [&](auto kern) { int QB; const unsigned g = attention_grid(FH, S, 256, &QB);
             hipLaunchKernelGGL(kern, dim3(g), dim3(256), 0, 0, (const T*)q, (const T*)k, (const T*)vt, o2, S, Sp, heads, D, FH, QB); };
-        auto v6 = [&](auto kern, auto nq_tag) { constexpr int NQ = decltype(nq_tag)::value; int QB; const unsigned g = att2_f16::attention6_grid<NQ>(FH, S, &QB);
+        auto v6 = [&](auto kern, auto nq_tag) { constexpr int NQ = decltype(nq_tag)::value; int QB; const unsigned g = attention_grid(FH, S, 128 * NQ, &QB);
             hipLaunchKernelGGL(kern, dim3(g), dim3(256), 0, 0, (const T*)q, (const T*)k, (const T*)vt, o2, S, Sp, heads, D, FH, QB); };
         if constexpr (F16) {
             if (getenv("ATTN_V6")) {   // round 6: NQ query tiles per wave (attention6.h: no guards -- the stress rows 5 .. 7 of (frame 0, head 0) are expected to fail)
-                timeit("v4 (library form)", [&] { v4(att2_f16::attention4_kernel<0>); });
-                timeit("v4 without guards (ABL 8)", [&] { v4(att2_f16::attention4_kernel<8>); });
-                timeit("v6 NQ = 2 (64 q/wave)", [&] { v6(att2_f16::attention6_kernel<2>, std::integral_constant<int, 2>{}); });
-                timeit("v6 NQ = 3 (96 q/wave)", [&] { v6(att2_f16::attention6_kernel<3>, std::integral_constant<int, 3>{}); });
-                timeit("v6 NQ = 4 (128 q/wave)", [&] { v6(att2_f16::attention6_kernel<4>, std::integral_constant<int, 4>{}); });
-                timeit("v4 (library form), again", [&] { v4(att2_f16::attention4_kernel<0>); });
-                timeit("v6 NQ = 4, again", [&] { v6(att2_f16::attention6_kernel<4>, std::integral_constant<int, 4>{}); });
-                timeit("v6 NQ = 4: no LDS reads", [&] { v6(att2_f16::attention6_kernel<4, 128>, std::integral_constant<int, 4>{}); });
-                timeit("v6 NQ = 4: no exp", [&] { v6(att2_f16::attention6_kernel<4, 1>, std::integral_constant<int, 4>{}); });
+                timeit("v4 (library form)", [&] { v4(attention4_kernel<T, 0>); });
+                timeit("v4 without guards (ABL 8)", [&] { v4(attention4_kernel<T, 8>); });
+                timeit("v6 NQ = 2 (64 q/wave)", [&] { v6(attention6_kernel<T, 2>, std::integral_constant<int, 2>{}); });
+                timeit("v6 NQ = 3 (96 q/wave)", [&] { v6(attention6_kernel<T, 3>, std::integral_constant<int, 3>{}); });
+                timeit("v6 NQ = 4 (128 q/wave)", [&] { v6(attention6_kernel<T, 4>, std::integral_constant<int, 4>{}); });
+                timeit("v4 (library form), again", [&] { v4(attention4_kernel<T, 0>); });
+                timeit("v6 NQ = 4, again", [&] { v6(attention6_kernel<T, 4>, std::integral_constant<int, 4>{}); });
+                timeit("v6 NQ = 4: no LDS reads", [&] { v6(attention6_kernel<T, 4, 128>, std::integral_constant<int, 4>{}); });
+                timeit("v6 NQ = 4: no exp", [&] { v6(attention6_kernel<T, 4, 1>, std::integral_constant<int, 4>{}); });
                 CK(hipFree(q)); CK(hipFree(k)); CK(hipFree(vt)); CK(hipFree(o2));
                 return;
             }
-            timeit("v4 (1 wave/SIMD, 64 q/wave)", [&] { v4(att2_f16::attention4_kernel<0>); });
-            timeit("v4 row sums on the matrix pipe", [&] { v4(att2_f16::attention4_kernel<0, true>); });
+            timeit("v4 (1 wave/SIMD, 64 q/wave)", [&] { v4(attention4_kernel<T, 0>); });
+            timeit("v4 row sums on the matrix pipe", [&] { v4(attention4_kernel<T, 0, true>); });
             if (abl) {
-                timeit("v4 abl: no exp", [&] { v4(att2_f16::attention4_kernel<1>); });
-                timeit("v4 abl: no barrier", [&] { v4(att2_f16::attention4_kernel<16>); });
-                timeit("v4 abl: no DMA", [&] { v4(att2_f16::attention4_kernel<2>); });
-                timeit("v4 abl: no LDS reads", [&] { v4(att2_f16::attention4_kernel<128>); });
-                timeit("v4 abl: MFMA + cvt only", [&] { v4(att2_f16::attention4_kernel<1 | 2 | 8 | 16 | 128>); });
+                timeit("v4 abl: no exp", [&] { v4(attention4_kernel<T, 1>); });
+                timeit("v4 abl: no barrier", [&] { v4(attention4_kernel<T, 16>); });
+                timeit("v4 abl: no DMA", [&] { v4(attention4_kernel<T, 2>); });
+                timeit("v4 abl: no LDS reads", [&] { v4(attention4_kernel<T, 128>); });
+                timeit("v4 abl: MFMA + cvt only", [&] { v4(attention4_kernel<T, 1 | 2 | 8 | 16 | 128>); });
                 auto clocked = [&](const char* name, auto kern) {
                     // shader-clock cycles (s_memtime) of one workgroup's three phases; the effective clock follows from the key
                     // loop's slot count and the wall time.  The stamps land in the first words of the output, which workgroup
@@ -184,43 +161,43 @@ struct Run {
                     CK(hipEventRecord(a)); v4(kern); CK(hipEventRecord(b)); CK(hipEventSynchronize(b));
                     float ms; CK(hipEventElapsedTime(&ms, a, b));
                     unsigned w3[3]; CK(hipMemcpy(w3, o2, 12, hipMemcpyDeviceToHost));
-                    int QB; const unsigned g = att2_f16::attention4_grid(FH, S, &QB);
+                    int QB; const unsigned g = attention_grid(FH, S, 256, &QB);
                     const double rounds = g / 256.0, ntiles = (S + 63) / 64, tot = (double)w3[0] + w3[1] + w3[2];
                     printf("%-26s prologue %u, key loop %u (%.1f per MFMA slot), epilogue %u cycles; %.3f ms -> %.2f GHz if every round took as long (%.1f rounds)\n",
                            name, w3[0], w3[1], w3[1] / (ntiles * 32), w3[2], ms, tot * rounds / (ms * 1e6), rounds);
                 };
-                clocked("v4 clock", att2_f16::attention4_kernel<256>);
-                clocked("v4 clock, MFMA + cvt only", att2_f16::attention4_kernel<256 | 1 | 2 | 8 | 16 | 128>);
+                clocked("v4 clock", attention4_kernel<T, 256>);
+                clocked("v4 clock, MFMA + cvt only", attention4_kernel<T, 256 | 1 | 2 | 8 | 16 | 128>);
             }
-            timeit("v2 QT1 max", [&] { v2(att2_f16::attention2_kernel<1, 0, 0, true>, 1); });
-            timeit("v2 QT1 opt (library)", [&] { v2(att2_f16::attention2_kernel<1, 0, 1, true>, 1); });
-            timeit("v2 K block 1 from global (ABL 32)", [&] { v2(att2_f16::attention2_kernel<1, 32, 1, true>, 1); });
-            timeit("v2 K odd d steps from global (ABL 64)", [&] { v2(att2_f16::attention2_kernel<1, 64, 1, true>, 1); });
-            timeit("v2 QT1 opt (library), again", [&] { v2(att2_f16::attention2_kernel<1, 0, 1, true>, 1); });
+            timeit("v2 QT1 max", [&] { v2(attention2_kernel<T, 1, 0, 0, true>, 1); });
+            timeit("v2 QT1 opt (library)", [&] { v2(attention2_kernel<T, 1, 0, 1, true>, 1); });
+            timeit("v2 K block 1 from global (ABL 32)", [&] { v2(attention2_kernel<T, 1, 32, 1, true>, 1); });
+            timeit("v2 K odd d steps from global (ABL 64)", [&] { v2(attention2_kernel<T, 1, 64, 1, true>, 1); });
+            timeit("v2 QT1 opt (library), again", [&] { v2(attention2_kernel<T, 1, 0, 1, true>, 1); });
             // (-DATTN_NO_V3: without the v3 instantiations.  The out-of-line safe pass is ONE function per translation unit: next
             // to attention3 (<= 256 registers) it is compiled with 178 and drags every attention2 variant here to 2 waves per
             // SIMD, while the library's (attention2 only) has 128 registers / 4 waves -- 3.5 ms here against 3.0 ms there.)
 #ifndef ATTN_NO_V3
             if (abl > 1) {
-                timeit("v3 8 waves, ring 5", [&] { v3(att2_f16::attention3_kernel<8, 5>, 8); });
-                timeit("v3 8 waves, ring 4", [&] { v3(att2_f16::attention3_kernel<8, 4>, 8); });
-                timeit("v3 4 waves, ring 4", [&] { v3(att2_f16::attention3_kernel<4, 4>, 4); });
+                timeit("v3 8 waves, ring 5", [&] { v3(attention3_kernel<T, 8, 5>, 8); });
+                timeit("v3 8 waves, ring 4", [&] { v3(attention3_kernel<T, 8, 4>, 8); });
+                timeit("v3 4 waves, ring 4", [&] { v3(attention3_kernel<T, 4, 4>, 4); });
             }
 #endif
             if (abl) {
-                timeit("v2 abl: no exp", [&] { v2(att2_f16::attention2_kernel<1, 1, 1, true>, 1); });
-                timeit("v2 abl: MFMA + cvt only", [&] { v2(att2_f16::attention2_kernel<1, 1 | 2 | 4 | 8 | 16, 1, true>, 1); });
+                timeit("v2 abl: no exp", [&] { v2(attention2_kernel<T, 1, 1, 1, true>, 1); });
+                timeit("v2 abl: MFMA + cvt only", [&] { v2(attention2_kernel<T, 1, 1 | 2 | 4 | 8 | 16, 1, true>, 1); });
 #ifndef ATTN_NO_V3
-                timeit("v3 abl: no exp", [&] { v3(att2_f16::attention3_kernel<8, 5, 1>, 8); });
-                timeit("v3 abl: no barrier", [&] { v3(att2_f16::attention3_kernel<8, 5, 16>, 8); });
+                timeit("v3 abl: no exp", [&] { v3(attention3_kernel<T, 8, 5, 1>, 8); });
+                timeit("v3 abl: no barrier", [&] { v3(attention3_kernel<T, 8, 5, 16>, 8); });
 #endif
             }
         } else {
-            timeit("v2 QT1 opt (library)", [&] { v2(att2_bf16::attention2_kernel<1, 0, 1, true>, 1); });
-            timeit("v4 (1 wave/SIMD, 64 q/wave)", [&] { v4(att2_bf16::attention4_kernel<0>); });
-            timeit("v4 row sums on the matrix pipe", [&] { v4(att2_bf16::attention4_kernel<0, true>); });
+            timeit("v2 QT1 opt (library)", [&] { v2(attention2_kernel<T, 1, 0, 1, true>, 1); });
+            timeit("v4 (1 wave/SIMD, 64 q/wave)", [&] { v4(attention4_kernel<T, 0>); });
+            timeit("v4 row sums on the matrix pipe", [&] { v4(attention4_kernel<T, 0, true>); });
 #ifndef ATTN_NO_V3
-            if (abl > 1) timeit("v3 8 waves, ring 5", [&] { v3(att2_bf16::attention3_kernel<8, 5>, 8); });
+            if (abl > 1) timeit("v3 8 waves, ring 5", [&] { v3(attention3_kernel<T, 8, 5>, 8); });
 #endif
         }
         CK(hipFree(q)); CK(hipFree(k)); CK(hipFree(vt)); CK(hipFree(o2));

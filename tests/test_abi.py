@@ -97,10 +97,10 @@ def test_adam_args_layout_matches_header():
 
 
 def test_m0_users(handle, tmp_path):
-    """csrc/common.h dtk_buffer_lds16 (and its copy in vit_attention4.h) writes m0 inside an asm statement the compiler cannot be
-    told about (hipcc refuses reserved registers in clobber lists), so the rule is structural: a kernel that contains the
-    descriptor form of LDS-DMA (`s_add_u32 m0, ...` + `buffer_load_dwordx4 ... lds`) has NO other instruction that reads or writes
-    m0.  Checked in the ISA of the built objects."""
+    """csrc/common.h dtk_buffer_lds16 writes m0 inside an asm statement the compiler cannot be told about (hipcc refuses
+    reserved registers in clobber lists), so the rule is structural: a kernel that contains the descriptor form of LDS-DMA
+    (`s_add_u32 m0, ...` + `buffer_load_dwordx4 ... lds`) has NO other instruction that reads or writes m0.  Checked in the
+    ISA of the built objects."""
     import os
     import re
     import subprocess
