@@ -477,11 +477,14 @@ __global__ __launch_bounds__(256) void select_kernel(dtk_geom g, const TileRec* 
 // triple-buffered 24 KB LDS tile of 32 cells filled by LDS-DMA (global_load_lds_dwordx4, no staging registers) and are
 // read once per wave as the A operand: one ds_read_b128 feeds two MFMAs, half the LDS traffic per flop of the tiled
 // kernel, and no correlation value ever leaves the registers.  In D a lane holds ONE source and 16 cells, so the
-// running top-4 of a source is lane-local: each value gets its 13-bit (step, register) position OR-ed into the low
-// mantissa bits (costs 2^-10 relative, covered by TRUNC_C in the candidate band) and is pushed through three v_med3 and
-// one v_max.  The cell <-> MFMA row assignment puts the cells on a checkerboard over the two lane halves, so a peak and
-// its neighbours split evenly between the two top-4 lists of a source.  The epilogue of step n-1 is
-// independent of the MFMAs of step n and is interleaved with them by the scheduler (one wave per SIMD: 512 VGPRs).
+// running top-6 of a source is lane-local.  Selection has two levels (peaks_group_op below): the 16 values of a group (one source
+// tile of one step) get their register index into the low 4 mantissa bits of the raw float and a sorted top-3 of the group is
+// kept with two v_med3_i32 and a v_max_i32; only the group's top-2 are turned into fixed-point keys (value << 13 | 13-bit (step,
+// register) position, costs 2^-10 relative, covered by TRUNC_C in the candidate band) and inserted into the lane's six-entry list
+// with five v_med3_i32 and one v_max_i32; the group's third value feeds a running maximum that sends the source to the exact tier
+// when it reaches the band.  The cell <-> MFMA row assignment puts the cells on a checkerboard over the two lane halves, so a peak
+// and its neighbours split evenly between the two lists of a source.  The selection of step n-1 is independent of the MFMAs of
+// step n and is interleaved with them slot by slot (one wave per SIMD: 512 VGPRs).
 constexpr int PK_SRC = 256;               // sources per workgroup
 constexpr int PK_CB = 1;                  // 32-cell blocks per step in production (2 = the four-accumulator variant: measured slower)
 constexpr int PK_IDX_BITS = 13;           // position tag: step << 5 | cell block << 4 | accumulator register
@@ -495,6 +498,7 @@ constexpr float EPS_PK = 2.1e-3f;
 typedef float f16v __attribute__((ext_vector_type(16)));
 constexpr size_t peaks_lds_bytes(int cb) { return 3 * (size_t)(32 * cb) * 384 * 2 + 64; }   // three tiles + the frame range (dynamic LDS)
 
+// (One-level program: corr_peaks_wide_kernel's, whose list work per MFMA slot is half; corr_peaks_kernel runs peaks_group_op below.)
 // Sorted top-6 insertion of one accumulator value as a program of eight VALU instructions: value -> key (fixed point -- the
 // accumulator already is 2^17 rho; negative values stay negative and never enter a list that starts at zero -- shifted above
 // the 13-bit position tag, which is wave-uniform: an SGPR operand), then one v_med3_i32 per list entry from the tail up and a
@@ -525,12 +529,61 @@ __device__ __forceinline__ void top_push_value(int (&v)[PK_TOP], float x, int ta
     top_push_op<4>(v, x, tag, key); top_push_op<5>(v, x, tag, key); top_push_op<6>(v, x, tag, key); top_push_op<7>(v, x, tag, key);
 }
 
+// Two-level selection of corr_peaks_kernel: 80 VALU instructions per group of 16 accumulator values (one source tile of one
+// 32-cell step) instead of 16 x 8 = 128, i.e. 3.3 instead of 5.3 per MFMA slot -- on the flat part of what a lone wave hides under
+// a 32x32x16 MFMA (profiles/r04_slot_rate_one_wave_per_simd.txt: <= 5 per slot, fragment reads and DMA requests included).
+//   Level 1 (61): value r -> t = (float bits & ~15) | r (v_and_or_b32, both constants inline), then the sorted top-3 g[0..2] of
+//     the group on these raw bits as signed integers (positive floats order as integers; negative ones have the sign bit set and
+//     never pass the zeros the first three values are compared against).
+//   Level 2 (2 x 9 + 1): g[0] and g[1] -> the fixed-point key of top_push_op ((int)x << PK_IDX_BITS | step tag | register:
+//     v_and_or_b32 with the wave-uniform step tag in an SGPR, v_cvt_i32_f32, v_lshl_or_b32) and its six-entry insertion;
+//     third = max(third, g[2]).
+// Why nothing is lost.  The accumulator is 2^17 rho < 2^20, so the four tag bits are fraction bits: (int)t == (int)x, and the
+// keys level 2 builds are bit for bit the keys top_push_op builds.  Level 1 orders by (float bits >> 4, register), which refines
+// the order of (int)x: a value level 1 ranks below another never has the larger integer part.  It may misorder values of EQUAL
+// integer part (whose keys differ in the position bits only), and it drops every value but the group's two largest.  Each dropped
+// value has an integer part <= that of its group's g[2] <= third, so its key is <= K3 = (int)third << PK_IDX_BITS | all position
+// bits.  The record epilogue tests K3 >= thr (thr = list maximum - band) once per source and frame:
+//   K3 <  thr: every dropped key is below thr <= the list maximum, so the true maximum was inserted, thr is the parent program's
+//              thr, and the keys >= thr -- all of them inserted -- occupy the list exactly as they would after inserting all 16
+//              values of every group: same candidates, same order, same sixth-entry test.  The record is identical.
+//   K3 >= thr: a dropped value may belong to the band (three band members in one group, or a misordered tie): the source goes
+//              to the exact tier (ncand = KC + 1), which needs no candidates.
+// The tag's 2^-19 relative perturbation never reaches a key, so EPS_PK's accounting is unchanged (tests/test_peaks_two_level.py).
+constexpr int PK_GRP_OPS = 80;
+template <int GI>
+__device__ __forceinline__ void peaks_group_op(const f16v& acc, int (&g)[3], int& k, int& key, int (&v)[PK_TOP], int& third, int stag) {
+    static_assert(PK_TOP == 6 && GI >= 0 && GI < PK_GRP_OPS, "the program is written out for six entries");
+    if constexpr (GI < 61) {
+        // values 0, 1, 2 take 2, 3, 4 instructions (the entries not yet filled are the constant 0), values 3 .. 15 four each
+        constexpr int r = GI < 2 ? 0 : GI < 5 ? 1 : GI < 9 ? 2 : 3 + (GI - 9) / 4;
+        constexpr int op = GI < 2 ? 3 * GI : GI < 5 ? (GI == 2 ? 0 : GI - 1) : GI < 9 ? GI - 5 : (GI - 9) % 4;
+        // op: 0 = tag, 1 = third entry, 2 = second entry, 3 = head
+        if constexpr (op == 0) asm("v_and_or_b32 %0, %1, -16, %2" : "=v"(k) : "v"(acc[r]), "i"(r));
+        else if constexpr (op == 1) {
+            if constexpr (r == 2) asm("v_med3_i32 %0, %1, 0, %2" : "=v"(g[2]) : "v"(g[1]), "v"(k));
+            else g[2] = med3_i32(g[1], g[2], k);
+        } else if constexpr (op == 2) {
+            if constexpr (r == 1) asm("v_med3_i32 %0, %1, 0, %2" : "=v"(g[1]) : "v"(g[0]), "v"(k));
+            else g[1] = med3_i32(g[0], g[1], k);
+        } else g[0] = r == 0 ? max(k, 0) : max(g[0], k);
+    } else if constexpr (GI < 79) {
+        constexpr int l = (GI - 61) % 9;
+        const int gx = g[(GI - 61) / 9];
+        if constexpr (l == 0) asm("v_and_or_b32 %0, %1, 15, %2" : "=v"(k) : "v"(gx), "s"(stag));   // step tag | register
+        else if constexpr (l == 1) key = (int)__int_as_float(gx);                                    // v_cvt_i32_f32
+        else if constexpr (l == 2) key = (key << PK_IDX_BITS) | k;                                   // v_lshl_or_b32
+        else if constexpr (l < 8) v[8 - l] = med3_i32(v[7 - l], v[8 - l], key);                      // entries 5, 4, 3, 2, 1
+        else v[0] = max(v[0], key);
+    } else third = max(third, g[2]);
+}
+
 // (The 192 source registers of a wave are only ever MFMA operands: loaded STRAIGHT INTO AGPRs by the asm that defines them, they
 // stay there -- the builtin MFMA takes a B operand from an AGPR as it is -- and everything the VALU touches (accumulators, lists,
 // fragment ring, addresses) fits the architectural VGPRs; left to the register allocator the kernel sat at exactly 256 VGPRs and
 // shuttled ~34 values per tile through v_accvgpr_read.)
 
-// VAR: development variants (DTK_DEBUG bits 8192 / 16384 / 32768): 1 = no top-N updates, 2 = no tile requests after the
+// VAR: development variants (DTK_DEBUG bits 8192 / 16384 / 32768): 1 = no selection (neither level), 2 = no tile requests after the
 // first two, 4 = no LDS reads.  0 in production.  (Measured with them: MFMAs alone 1.63 PF; + LDS reads or + DMA alone
 // unchanged; both 1.22 PF; + list updates 0.90 PF.  Staging the tiles through registers instead of LDS-DMA: 0.39 PF.)
 template <int I, int N, class F>
@@ -678,6 +731,7 @@ __global__ __launch_bounds__(256) void corr_peaks_kernel(dtk_geom g, const half_
         for (int t = 0; t < 2; ++t)
 #pragma unroll
             for (int k = 0; k < PK_TOP; ++k) v[t][k] = 0;
+        int third[2] = {0, 0};   // running maximum (raw tagged float bits) of the groups' third values: what level 1 dropped
         // one step: the MFMAs of the tile in `buf` into accN[cell block][source tile], interleaved with the list updates of
         // the previous tile's accP (step index np)
         auto step = [&](int buf, f16v (&accN)[CB][2], const f16v (&accP)[CB][2], int np) {
@@ -689,35 +743,45 @@ __global__ __launch_bounds__(256) void corr_peaks_kernel(dtk_geom g, const half_
             };
             const int ib = np << TSH;
             const f16v zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};   // inline constant C
-            int keys[2] = {0, 0};   // the key of the value whose insertion is in flight (one per source tile at most)
+            // per source tile: the group's top-3, the tagged value / position in flight, the key in flight
+            int grp[2][3], tg[2] = {0, 0}, keys[2] = {0, 0};
             h8 a[3];
             a[0] = frag(0);
             a[1] = frag(1);
             constexpr int NF = KS * CB;          // A fragments of the tile: fragment fr = k-step fr / CB, cell block fr % CB
-            constexpr int NSLOT = 2 * NF, NINS = 32 * CB * 8;   // MFMA slots; list instructions (32 CB values x 8)
+            constexpr int NSLOT = 2 * NF, NINS = 2 * CB * PK_GRP_OPS;   // MFMA slots; selection instructions (2 CB groups x 80)
             // (compile-time recursion instead of `#pragma unroll`: at 96 slots the unroller gives up and the accumulators'
             // indices become run-time -- scratch memory)
             peaks_static_for<0, NSLOT>([&](auto qc) {
                 constexpr int q = decltype(qc)::value, fr = q / 2, t = q % 2, ks = fr / CB, cb = fr % CB;
                 if (t == 0 && fr + 2 < NF && !(VAR & 4)) a[(fr + 2) % 3] = frag(fr + 2);
                 accN[cb][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[fr % 3], bs[t][ks], ks == 0 ? zero16 : accN[cb][t], 0, 0, 0);
-                // the list instructions of the previous tile, spread evenly over the MFMA slots: slot q issues instructions
-                // [NINS q / NSLOT, NINS (q + 1) / NSLOT) of the stream; value e = index / 8 is accumulator register e / (2 CB) of
-                // (source tile e & 1, cell block (e >> 1) % CB); position tag = step << 5 | cell block << 4 | register
+                // the selection instructions of the previous tile, spread evenly over the MFMA slots (3 or 4 per slot): slot q
+                // issues instructions [NINS q / NSLOT, NINS (q + 1) / NSLOT) of the stream; the two source tiles alternate
+                // instruction by instruction (i & 1), each running the group programs of its cell blocks one after the other;
+                // position tag = step << TSH | cell block << 4 | register
                 peaks_static_for<q * NINS / NSLOT, (q + 1) * NINS / NSLOT>([&](auto ic) {
-                    constexpr int i = decltype(ic)::value, e = i >> 3, lt = e & 1, lcb = (e >> 1) % CB, lr = e / (2 * CB);
-                    if (!(VAR & 1) || e == 0) top_push_op<(i & 7)>(v[lt], accP[lcb][lt][lr], ib | (lcb << 4) | lr, keys[lt]);
+                    constexpr int i = decltype(ic)::value, lt = i & 1, lcb = (i >> 1) / PK_GRP_OPS, gi = (i >> 1) % PK_GRP_OPS;
+                    // VAR & 1: both levels off (value 0's tag and head, folded into `third`, keep the accumulators alive)
+                    if constexpr (!(VAR & 1))
+                        peaks_group_op<gi>(accP[lcb][lt], grp[lt], tg[lt], keys[lt], v[lt], third[lt], ib | (lcb << 4));
+                    else if constexpr (lcb == 0 && gi < 2)
+                        peaks_group_op<gi>(accP[lcb][lt], grp[lt], tg[lt], keys[lt], v[lt], third[lt], ib | (lcb << 4));
+                    else if constexpr (lcb == 0 && gi == PK_GRP_OPS - 1)
+                        third[lt] = max(third[lt], grp[lt][0]);
                 });
                 __builtin_amdgcn_sched_barrier(0);
             });
         };
+        // the last tile's groups, after the loop (nothing to hide them under)
         auto epi = [&](const f16v (&acc)[CB][2], int np) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-#pragma unroll
-                for (int cb = 0; cb < CB; ++cb)
-#pragma unroll
-                    for (int t = 0; t < 2; ++t) top_push_value(v[t], acc[cb][t][r], (np << TSH) | (cb << 4) | r);
+            peaks_static_for<0, 2 * CB>([&](auto gc) {
+                constexpr int t = decltype(gc)::value & 1, cb = decltype(gc)::value >> 1;
+                int grp[3], tg, key;
+                peaks_static_for<0, PK_GRP_OPS>([&](auto ic) {
+                    peaks_group_op<decltype(ic)::value>(acc[cb][t], grp, tg, key, v[t], third[t], (np << TSH) | (cb << 4));
+                });
+            });
         };
         f16v accA[CB][2], accB[CB][2];
 #pragma unroll
@@ -760,6 +824,8 @@ __global__ __launch_bounds__(256) void corr_peaks_kernel(dtk_geom g, const half_
             int o[PK_TOP];
 #pragma unroll
             for (int k = 0; k < PK_TOP; ++k) o[k] = __shfl(v[t][k], lane ^ 32, WAVE);
+            // what level 1 dropped anywhere in the map is <= K3 (peaks_group_op): integer part of the larger `third`, all position bits
+            const int k3 = ((int)__int_as_float(max(third[t], __shfl(third[t], lane ^ 32, WAVE))) << PK_IDX_BITS) | ((1 << PK_IDX_BITS) - 1);
             const int i = src0 + t * 32 + j;
             if (h == 0 && tf[t] == f) {
                 const int amax_i = max(v[t][0], o[0]);
@@ -782,8 +848,9 @@ __global__ __launch_bounds__(256) void corr_peaks_kernel(dtk_geom g, const half_
                         ++nc;
                     }
                 }
-                // a last list entry inside the band may hide a further one; a maximum inside the band of zero decides nothing
-                if (v[t][PK_TOP - 1] >= thr || o[PK_TOP - 1] >= thr || thr <= 0) nc = KC + 1;
+                // a last list entry inside the band may hide a further one, and so may a group's third value; a maximum inside
+                // the band of zero decides nothing
+                if (v[t][PK_TOP - 1] >= thr || o[PK_TOP - 1] >= thr || k3 >= thr || thr <= 0) nc = KC + 1;
                 const float amax = (float)(amax_i >> PK_IDX_BITS) * (1.f / (float)(1 << PK_VAL_BITS));
                 rr->amax = amax;
                 rr->zmax = 0.f;
