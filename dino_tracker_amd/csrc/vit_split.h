@@ -1,7 +1,5 @@
 // vit_split.h -- the ESCALATED precision of the ViT encoder (round 6): every matrix product of a block on split 16-bit operands.
 //
-// Included by vit.hip inside its anonymous namespace (it uses Vec / IsF16 / mfma16 / mfma32 / gswz / operand_mode / wave_sum).
-//
 // Why.  With plain fp16 operands every stored activation and weight is rounded to 11 significant bits; an emulation of exactly
 // these roundings in float64 (scripts/p1_error_budget.py) reproduces the measured feature error of the fast path -- 1.3e-4
 // relative on the benchmark weights, 5.8e-4 with LayerScale 1.0, 2.1e-3 with DINOv2-like outlier statistics -- and shows that
@@ -25,6 +23,10 @@
 //                            lane-local), 4 waves x 32 queries per workgroup, 64-key tiles staged through LDS, plain online
 //                            softmax in fp32 (running maximum, rescale every tile), P carried as hi + lo with a 2^10 scale so
 //                            that small probabilities stay normal numbers.
+#pragma once
+#include "vit_gemm_common.h"
+
+namespace {
 
 constexpr int SP_M = 128, SP_N = 128, SP_K = 32;
 enum { SEPI_QKV = 0, SEPI_GELU = 1, SEPI_RESID = 2, SEPI_F32 = 3 };
@@ -315,7 +317,7 @@ __global__ __launch_bounds__(512, 1) void gemm_split_dma_kernel(const T* __restr
     const int wr = w >> 1, wc = w & 1;
     const int fj = lane & 15, fg = lane >> 4;
     // request q = 6 w + i: 0..15 A_hi rows 16 q.., 16..31 A_lo, 32..39 W_hi rows n0 + 16 (q - 32).., 40..47 W_lo
-    // (descriptor LDS-DMA, vit.hip wd_issue: the request's LDS slot is q KB into the stage)
+    // (descriptor LDS-DMA, vit_gemm_common.h wd_issue: the request's LDS slot is q KB into the stage)
     dtk_u4 srd[SD_REQ];
     unsigned voff[SD_REQ];
 #pragma unroll
@@ -325,7 +327,7 @@ __global__ __launch_bounds__(512, 1) void gemm_split_dma_kernel(const T* __restr
         const int blk = isA ? (q & 15) : ((q - 32) & 7);
         const bool lo = isA ? q >= 16 : q >= 40;
         const int row = blk * 16 + (lane >> 2);
-        const int piece = (lane & 3) ^ ((0x1230 >> (((row >> 2) & 3) * 4)) & 3);
+        const int piece = (lane & 3) ^ ((0x1230 >> (((row >> 2) & 3) * 4)) & 3);   // gswz_f(row) spelled out: the call changes the code
         const int trow = isA ? (int)(min(m0 + row, M - 1) - m0) : row;
         srd[i] = dtk_make_srd(isA ? (lo ? Al : Ah) + m0 * K : (lo ? Wl : Wh) + (long long)n0 * K);
         voff[i] = (unsigned)(trow * K + piece * 8) * 2u;
@@ -341,7 +343,7 @@ __global__ __launch_bounds__(512, 1) void gemm_split_dma_kernel(const T* __restr
     for (int mi = 0; mi < 4; ++mi)
 #pragma unroll
         for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = f4{0.f, 0.f, 0.f, 0.f};
-    const int fsw = (0x1230 >> (((fj >> 2) & 3) * 4)) & 3;
+    const int fsw = gswz_f(fj);
     const unsigned a_off = ((wr * 64 + fj) * 4 + (fg ^ fsw)) * 16;
     const unsigned b_off = 2 * SD_M * 64 + ((wc * 64 + fj) * 4 + (fg ^ fsw)) * 16;
     issue(0, 0);
@@ -376,7 +378,7 @@ __global__ __launch_bounds__(512, 1) void gemm_split_dma_kernel(const T* __restr
     dtk_vm_wait<0>();
     float amax = 0.f;
     typedef typename Vec<T>::t4 T4;
-    // Round 6: the epilogues leave through LDS as whole rows (vit.hip, gemm_wide_kernel: one workgroup per CU, nothing overlaps the
+    // Round 6: the epilogues leave through LDS as whole rows (vit_gemm_wide.h, gemm_wide_kernel: one workgroup per CU, nothing overlaps the
     // epilogue, and its 8-byte pieces -- 16 tokens x 32 B per store instruction -- ran at 1.5 TB/s).  The stages are dead here.
     static_assert(2 * SD_M * SD_OPITCH <= SD_STAGES * SD_STAGE_BYTES && SD_M * SD_FPITCH <= SD_STAGES * SD_STAGE_BYTES, "staged tile must fit");
     if (STAGED && (EPI == SEPI_GELU || (EPI == SEPI_QKV && n0 < 2 * e.D))) {
@@ -416,20 +418,19 @@ __global__ __launch_bounds__(512, 1) void gemm_split_dma_kernel(const T* __restr
 #pragma unroll 4
         for (int it = 0; it < SD_M / 16; ++it) {
             const int row = it * 16 + (tid >> 5);
-            const unsigned char* sp = stages + plane * (SD_M * SD_OPITCH) + row * SD_OPITCH + piece * 16;
-            const uint2 lo = *reinterpret_cast<const uint2*>(sp), hi = *reinterpret_cast<const uint2*>(sp + 8);
+            const uint4 v = staged16(stages + plane * (SD_M * SD_OPITCH) + row * SD_OPITCH + piece * 16);
             const long long m = m0 + row;
             if (m < M) {
                 if (EPI == SEPI_GELU) {
-                    *reinterpret_cast<uint4*>(dst + m * N) = make_uint4(lo.x, lo.y, hi.x, hi.y);
+                    *reinterpret_cast<uint4*>(dst + m * N) = v;
                 } else {
                     const unsigned f = (unsigned)m / (unsigned)e.S, pos = (unsigned)m - f * (unsigned)e.S;   // (M < 2^31 tokens)
-                    *reinterpret_cast<uint4*>(dst + (((size_t)f * e.heads + hh) * e.Sp + pos) * 64) = make_uint4(lo.x, lo.y, hi.x, hi.y);
+                    *reinterpret_cast<uint4*>(dst + (((size_t)f * e.heads + hh) * e.Sp + pos) * 64) = v;
                 }
             }
         }
     } else if (STAGED && EPI == SEPI_QKV) {
-        // V^T tiles (vit.hip, gemm_wide_kernel): both planes staged TRANSPOSED -- sT[feature][token], 16-bit, 520-byte rows -- and written
+        // V^T tiles (vit_gemm_wide.h, gemm_wide_kernel): both planes staged TRANSPOSED -- sT[feature][token], 16-bit, 520-byte rows -- and written
         // as 8-byte pieces of four tokens along a feature row where positions come in fours, element by element otherwise
         static_assert(2 * SD_N * (SD_M * 2 + 8) <= SD_STAGES * SD_STAGE_BYTES, "transposed planes must fit");
         constexpr int TP = SD_M * 2 + 8;
@@ -731,3 +732,5 @@ __global__ __launch_bounds__(256, 2) void attention_split_kernel(const T* __rest
 #undef AS_FETCH
 #undef AS_PUT
 }
+
+}  // namespace

@@ -15,9 +15,9 @@ def _src(name):
 
 
 def test_gelu_polynomial_error_bound():
-    """gelu2() in vit.hip: erf(s / sqrt 2) ~ s P(s^2) on |s| <= c, evaluated in fp32 exactly as the kernel does
+    """gelu2() in vit_gemm_common.h: erf(s / sqrt 2) ~ s P(s^2) on |s| <= c, evaluated in fp32 exactly as the kernel does
     (Horner with fused multiply-adds ~ float32 arithmetic here); claimed |GELU error| < 6e-5 everywhere."""
-    src = _src("vit.hip")
+    src = _src("vit_gemm_common.h")
     body = src[src.index("__device__ __forceinline__ f2 gelu2(f2 x)"):]
     body = body[:body.index("return __builtin_elementwise_fma(hx, e, hx);")]
     clamp = float(re.search(r"const f2 c = \{([0-9.eE+-]+)f", body).group(1))
