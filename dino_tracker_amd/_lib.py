@@ -51,6 +51,15 @@ class VitModel(ctypes.Structure):
 VIT_TILED_GEMMS, VIT_BF16, VIT_CHECK_RANGE, VIT_ATTENTION_V2, VIT_GEMM_WS_V1, VIT_ATTENTION_V4, VIT_GEMM_WIDE_V1, VIT_NO_LN_FUSION = 1, 2, 4, 8, 16, 32, 64, 128  # dtk_vit_model.flags
 OPERAND_F16, OPERAND_BF16, OPERAND_ATTENTION_V2, OPERAND_ATTENTION_V4 = 0, 1, 0x100, 0x2000
 OPERAND_ATTENTION_V5, OPERAND_ATTENTION_V5_INPHASE = 0x200, 0x400   # stand-alone stage only: the round-5 experiment kernel (vit_attention5.h)
+VIT_GEMM_QKV, VIT_GEMM_QKV_FACET, VIT_GEMM_PROJ, VIT_GEMM_FC1, VIT_GEMM_FC2 = 0, 1, 2, 3, 4   # dtk_vit_gemm_args.role
+
+
+class VitGemmArgs(ctypes.Structure):
+    """struct dtk_vit_gemm_args (include/dtk.h): one GEMM of a block on its own (dtk_vit_gemm / dtk_vit_gemm_split)."""
+    _fields_ = ([(n, ctypes.c_int32) for n in ("role", "D", "flags", "operand_type")] + [("rows", ctypes.c_int64)] +
+                [("S", ctypes.c_int32), ("Sp", ctypes.c_int32), ("ln_eps", ctypes.c_float), ("w_scale", ctypes.c_float)] +
+                [(n, c_void_p) for n in ("a", "a_lo", "w", "w_lo", "bias", "gamma", "q", "k", "vt", "q_lo", "k_lo", "vt_lo", "out",
+                                         "out_lo", "out_f32", "x", "ln_x", "ln_w", "ln_b", "ln_out", "ovf")])
 
 
 class TrackOpts(ctypes.Structure):
@@ -97,6 +106,8 @@ SIGNATURES = {
                                 c_void_p, c_size_t, c_void_p]),
     "dtk_vit_attention": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "dtk_vit_attention_split": (c_int, [c_void_p] * 8 + [c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "dtk_vit_gemm": (c_int, [ctypes.POINTER(VitGemmArgs), c_void_p]),
+    "dtk_vit_gemm_split": (c_int, [ctypes.POINTER(VitGemmArgs), c_void_p]),
     "dtk_delta_dino_packed_floats": (c_size_t, [c_int, c_int]),
     "dtk_delta_dino_pack": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float,
                                     c_void_p, c_void_p]),

@@ -436,17 +436,18 @@ struct GemmPath {
     bool wide_v1;  // DTK_VIT_GEMM_WIDE_V1: the LDS-DMA kernels (split one included) without half-step prefetch / staged epilogues (A / B)
     bool fc2_ln;   // fc2 of a block may carry the next block's LayerNorm-1 (vit_run: when that block exists and is a fast one)
 };
-inline GemmPath gemm_path(const dtk_vit_model* m) {
-    const int f = m->flags;
-    const bool tiled = (f & DTK_VIT_TILED_GEMMS) != 0, ws = !tiled && m->D == WS_K, wide_v1 = (f & DTK_VIT_GEMM_WIDE_V1) != 0;
+inline GemmPath gemm_path(int D, int f) {
+    const bool tiled = (f & DTK_VIT_TILED_GEMMS) != 0, ws = !tiled && D == WS_K, wide_v1 = (f & DTK_VIT_GEMM_WIDE_V1) != 0;
     static_assert(WS_K == WD_N, "fc2 of the weight-stationary width is gemm_wide_delta_kernel's shape");
-    return {tiled, ws, !tiled && m->D % W2_N == 0, (f & DTK_VIT_GEMM_WS_V1) != 0, wide_v1, ws && !wide_v1 && !(f & DTK_VIT_NO_LN_FUSION)};
+    return {tiled, ws, !tiled && D % W2_N == 0, (f & DTK_VIT_GEMM_WS_V1) != 0, wide_v1, ws && !wide_v1 && !(f & DTK_VIT_NO_LN_FUSION)};
 }
+inline GemmPath gemm_path(const dtk_vit_model* m) { return gemm_path(m->D, m->flags); }
 
 // One GEMM of a fast block, C[rows][N] = A[rows][K] . W[N][K]^T with epilogue EPI.  First match wins:
 //
 //   EPI_F32 (the qkv facet)             gemm_tiled_kernel<T, EPI_F32>, always
 //   path.ws, K = 384 (qkv, proj, fc1)   gemm_ws_kernel<T, EPI>            (ws_v1: <T, EPI, 0>)           gemm_ws_grid(N)     x 256
+//                                       (not the qkv of SEVERAL frames shorter than its 32-row tile, S < 32: those fall through to the last line)
 //   path.ws, K != 384 (fc2: N = 384)    gemm_wide_delta_kernel<T>         (wide_v1: <T, false>;          rows / 256          x 512
 //                                                                          e.ln_out set: <T, true, true>)
 //   path.wide                           gemm_wide_kernel<T, EPI>          (wide_v1: <T, EPI, false>)     gemm_wide_grid(N)   x 512
@@ -457,7 +458,11 @@ template <typename T, int EPI>
 int launch_gemm(const char* name, const GemmPath& path, const T* A, const T* W, long long rows, int N, int K, const GemmEpi<T>& e,
                 hipStream_t st) {
     if constexpr (EPI != EPI_F32) {
-        if (path.ws && K == WS_K) {
+        // (gemm_ws_kernel's QKV epilogue steps (frame, position) a tile at a time and lets a tile cross ONE frame end: S >= WS_ROWS.
+        //  SEVERAL shorter frames -- under 49 x 49 pixels -- put Q / K rows into the padding of the wrong frame; the tiled kernel divides
+        //  per row.)
+        const bool ws_fits = EPI != EPI_QKV || e.S >= WS_ROWS || rows <= e.S;
+        if (path.ws && K == WS_K && ws_fits) {
             const auto gr = gemm_ws_grid(N, rows);
             if (path.ws_v1)
                 DTK_LAUNCH(name, (gemm_ws_kernel<T, EPI, 0>), gr.first, dim3(256), 0, st, A, W, rows, N, e, gr.second);
@@ -683,6 +688,99 @@ int vit_run(const dtk_vit_model* m, const float* frames, int nframes, int video_
     return DTK_OK;
 }
 
+// ---- one GEMM of a block on its own (dtk_vit_gemm / dtk_vit_gemm_split) ------------------------------------------------------------
+// The role names the shape and the epilogue; the kernel is what launch_gemm / launch_gemm_split choose for a model of width D with
+// these flags (gemm_path: the dispatch of vit_run, no second table), under the launch names of vit_run.
+int vit_gemm_check(const dtk_vit_gemm_args* g, const char* who, bool split, int* N, int* K) {
+    DTK_REQUIRE(g, "%s: null pointer", who);
+    DTK_REQUIRE(g->D == 384 || g->D == 768 || g->D == 1024, "%s: D must be 384, 768 or 1024 (got %d)", who, g->D);
+    DTK_REQUIRE(g->operand_type == DTK_OPERAND_F16 || g->operand_type == DTK_OPERAND_BF16, "%s: operand_type", who);
+    DTK_REQUIRE(g->rows > 0 && g->rows < (1ll << 31), "%s: rows", who);
+    DTK_REQUIRE(g->a && g->w && (!split || (g->a_lo && g->w_lo)), "%s: null operand", who);
+    const int D = g->D;
+    switch (g->role) {
+        case DTK_VIT_GEMM_QKV:
+            *N = 3 * D; *K = D;
+            DTK_REQUIRE(g->q && g->k && g->vt && (!split || (g->q_lo && g->k_lo && g->vt_lo)), "%s: QKV needs q, k and vt", who);
+            DTK_REQUIRE(g->S > 0 && g->Sp >= g->S && g->Sp % 64 == 0 && g->rows % g->S == 0,
+                        "%s: bad sizes (Sp %% 64 == 0, Sp >= S, rows a multiple of S)", who);
+            break;
+        case DTK_VIT_GEMM_QKV_FACET:
+            *N = 3 * D; *K = D;
+            DTK_REQUIRE(g->out_f32, "%s: QKV_FACET needs out_f32", who);
+            break;
+        case DTK_VIT_GEMM_FC1:
+            *N = 4 * D; *K = D;
+            DTK_REQUIRE(g->out && (!split || g->out_lo), "%s: FC1 needs out", who);
+            break;
+        case DTK_VIT_GEMM_PROJ:
+        case DTK_VIT_GEMM_FC2:
+            *N = D; *K = g->role == DTK_VIT_GEMM_FC2 ? 4 * D : D;
+            DTK_REQUIRE(g->gamma && (split ? g->x != nullptr : g->out != nullptr), "%s: PROJ / FC2 need gamma and %s", who, split ? "x" : "out");
+            break;
+        default:
+            DTK_REQUIRE(false, "%s: unknown role %d", who, g->role);
+    }
+    return DTK_OK;
+}
+
+template <typename T>
+int vit_gemm_stage(const dtk_vit_gemm_args* g, int N, int K, hipStream_t st) {
+    const GemmPath path = gemm_path(g->D, g->flags);
+    const T *A = reinterpret_cast<const T*>(g->a), *W = reinterpret_cast<const T*>(g->w);
+    int* const epi_ovf = IsF16<T>::value ? g->ovf : nullptr;
+    GemmEpi<T> e{};
+    e.bias = g->bias;
+    switch (g->role) {
+        case DTK_VIT_GEMM_QKV:
+            e.q = reinterpret_cast<T*>(g->q); e.k = reinterpret_cast<T*>(g->k); e.vt = reinterpret_cast<T*>(g->vt);
+            e.S = g->S; e.Sp = g->Sp; e.heads = g->D / 64; e.D = g->D; e.qscale = 0.125f * 1.4426950408889634f; e.ovf = epi_ovf;
+            return launch_gemm<T, EPI_QKV>("vit_gemm_qkv", path, A, W, g->rows, N, K, e, st);
+        case DTK_VIT_GEMM_QKV_FACET:
+            e.out_f32 = g->out_f32;
+            return launch_gemm<T, EPI_F32>("vit_gemm_qkv_facet", path, A, W, g->rows, N, K, e, st);
+        case DTK_VIT_GEMM_FC1:
+            e.out = reinterpret_cast<T*>(g->out); e.ovf = epi_ovf;
+            return launch_gemm<T, EPI_GELU>("vit_gemm_fc1", path, A, W, g->rows, N, K, e, st);
+        default:
+            e.delta = reinterpret_cast<T*>(g->out); e.gamma = g->gamma;
+            if (g->ln_out) {   // the next block's LayerNorm inside fc2's epilogue: where vit_run fuses it, nowhere else
+                DTK_REQUIRE(g->role == DTK_VIT_GEMM_FC2 && path.fc2_ln, "dtk_vit_gemm: the fused LayerNorm is fc2's at D = 384 without TILED_GEMMS / GEMM_WIDE_V1 / NO_LN_FUSION");
+                DTK_REQUIRE(g->ln_x && g->ln_w && g->ln_b, "dtk_vit_gemm: the fused LayerNorm needs ln_x, ln_w and ln_b");
+                e.ln_x = g->ln_x; e.ln_w = g->ln_w; e.ln_b = g->ln_b; e.ln_out = reinterpret_cast<T*>(g->ln_out); e.ln_eps = g->ln_eps;
+                e.ln_ovf = g->ovf;
+            }
+            return launch_gemm<T, EPI_DELTA>(g->role == DTK_VIT_GEMM_PROJ ? "vit_gemm_proj" : "vit_gemm_fc2", path, A, W, g->rows, N, K, e, st);
+    }
+}
+
+template <typename T>
+int vit_gemm_split_stage(const dtk_vit_gemm_args* g, int N, int K, hipStream_t st) {
+    const GemmPath path = gemm_path(g->D, g->flags);
+    const T *Ah = reinterpret_cast<const T*>(g->a), *Al = reinterpret_cast<const T*>(g->a_lo);
+    const T *Wh = reinterpret_cast<const T*>(g->w), *Wl = reinterpret_cast<const T*>(g->w_lo);
+    int* const epi_ovf = IsF16<T>::value ? g->ovf : nullptr;
+    SplitEpi<T> se{};
+    se.bias = g->bias; se.inv_wscale = 1.f / (g->w_scale > 0.f ? g->w_scale : 1.f);
+    switch (g->role) {
+        case DTK_VIT_GEMM_QKV:
+            se.q_hi = reinterpret_cast<T*>(g->q); se.q_lo = reinterpret_cast<T*>(g->q_lo); se.k_hi = reinterpret_cast<T*>(g->k);
+            se.k_lo = reinterpret_cast<T*>(g->k_lo); se.vt_hi = reinterpret_cast<T*>(g->vt); se.vt_lo = reinterpret_cast<T*>(g->vt_lo);
+            se.S = g->S; se.Sp = g->Sp; se.heads = g->D / 64; se.D = g->D; se.qscale = 0.125f * 1.4426950408889634f; se.ovf = epi_ovf;
+            return launch_gemm_split<T, SEPI_QKV>("vit_gemm_qkv_split", path, Ah, Al, Wh, Wl, g->rows, N, K, se, st);
+        case DTK_VIT_GEMM_QKV_FACET:
+            se.out_f32 = g->out_f32;
+            return launch_gemm_split<T, SEPI_F32>("vit_gemm_qkv_facet", path, Ah, Al, Wh, Wl, g->rows, N, K, se, st);
+        case DTK_VIT_GEMM_FC1:
+            se.out_hi = reinterpret_cast<T*>(g->out); se.out_lo = reinterpret_cast<T*>(g->out_lo); se.ovf = epi_ovf;
+            return launch_gemm_split<T, SEPI_GELU>("vit_gemm_fc1_split", path, Ah, Al, Wh, Wl, g->rows, N, K, se, st);
+        default:
+            se.x = g->x; se.gamma = g->gamma;
+            return launch_gemm_split<T, SEPI_RESID>(g->role == DTK_VIT_GEMM_PROJ ? "vit_gemm_proj_split" : "vit_gemm_fc2_split", path, Ah, Al,
+                                                    Wh, Wl, g->rows, N, K, se, st);
+    }
+}
+
 }  // namespace
 
 extern "C" size_t dtk_vit_workspace_bytes(const dtk_vit_model* m, int video_h, int video_w, int frames) {
@@ -758,3 +856,22 @@ extern "C" int dtk_vit_attention_split(const void* q_hi, const void* q_lo, const
     return DTK_OK;
 }
 
+
+// One GEMM of a block on its own (tests compare every kernel form with float64 on the operands it read; layouts and dispatch as
+// inside dtk_vit_forward).
+extern "C" int dtk_vit_gemm(const dtk_vit_gemm_args* g, void* stream) {
+    int N = 0, K = 0;
+    if (const int rc = vit_gemm_check(g, "dtk_vit_gemm", false, &N, &K)) return rc;
+    if (g->operand_type == DTK_OPERAND_BF16) return vit_gemm_stage<__bf16>(g, N, K, dtk_stream(stream));
+    return vit_gemm_stage<_Float16>(g, N, K, dtk_stream(stream));
+}
+
+// The same stage on split operands (vit_split.h): hi / lo planes of A, of w_scale * W and of the 16-bit outputs; the residual roles
+// add their update to the fp32 stream x.
+extern "C" int dtk_vit_gemm_split(const dtk_vit_gemm_args* g, void* stream) {
+    int N = 0, K = 0;
+    if (const int rc = vit_gemm_check(g, "dtk_vit_gemm_split", true, &N, &K)) return rc;
+    DTK_REQUIRE(!g->ln_out, "dtk_vit_gemm_split: the split blocks have their own LayerNorm");
+    if (g->operand_type == DTK_OPERAND_BF16) return vit_gemm_split_stage<__bf16>(g, N, K, dtk_stream(stream));
+    return vit_gemm_split_stage<_Float16>(g, N, K, dtk_stream(stream));
+}

@@ -162,7 +162,8 @@ __device__ __forceinline__ void wd_issue(const dtk_u4 (&srd)[REQ], const unsigne
 }
 
 // GELU(x) = x Phi(x) with erf(s / sqrt 2) ~ s P(s^2) on |s| <= 4.25 (odd minimax polynomial, 9 coefficients, |err| < 2e-5;
-// |GELU error| < 6e-5 everywhere, far below the bf16 rounding of the result); two values per packed fp32 instruction
+// |GELU error| < 6e-5 for x >= -12, far below the bf16 rounding of the result; below that the clamp leaves x / 2 * (1 + erf~(-4.25 / sqrt 2)),
+// about 4.8e-6 |x| where GELU is 0 -- measured by tests/test_gpu_vit_gemm.py); two values per packed fp32 instruction
 __device__ __forceinline__ f2 gelu2(f2 x) {
     const f2 c = {4.25f, 4.25f};
     const f2 sx = __builtin_elementwise_min(__builtin_elementwise_max(x, -c), c);

@@ -174,6 +174,43 @@ int dtk_vit_attention_split(const void* q_hi, const void* q_lo, const void* k_hi
                             const void* vt_lo, void* out_hi, void* out_lo, int frames, int heads, int S, int Sp, int operand_type,
                             void* stream);
 
+/* ONE GEMM of a block on its own: C = A W^T with the epilogue of its role, on exactly the kernel dtk_vit_forward runs for a model
+ * of width D (384, 768 or 1024) with the DTK_VIT_* bits `flags` (the GEMM bits: TILED_GEMMS, GEMM_WS_V1, GEMM_WIDE_V1,
+ * NO_LN_FUSION).  The role fixes N x K and what is written:
+ *   DTK_VIT_GEMM_QKV        3D x D    q / k [rows / S][D / 64][Sp][64], vt [rows / S][D / 64][64][Sp]; q scaled by log2(e) / 8.  rows is a
+ *                                     multiple of S; the caller zeroes the padding s >= S (dtk_vit_forward does), it is not written
+ *   DTK_VIT_GEMM_QKV_FACET  3D x D    out_f32 [rows][3D] = A W^T + bias
+ *   DTK_VIT_GEMM_PROJ       D x D     out [rows][D] = gamma * (A W^T + bias), 16-bit (the pending residual update)
+ *   DTK_VIT_GEMM_FC1        4D x D    out [rows][4D] = GELU(A W^T + bias), 16-bit
+ *   DTK_VIT_GEMM_FC2        D x 4D    as PROJ.  With ln_out set (D = 384, none of TILED_GEMMS / GEMM_WIDE_V1 / NO_LN_FUSION: where
+ *                                     dtk_vit_forward fuses it) the update is NOT stored: ln_x [rows][D] += it and ln_out [rows][D] =
+ *                                     LayerNorm(ln_x; ln_w, ln_b, ln_eps), 16-bit
+ * a [rows][K] and w [N][K] are 16-bit in `operand_type`, bias / gamma fp32 [N].  ovf: optional device word, OR-ed with 2 (QKV) / 4
+ * (FC1) when a stored value reaches the fp16 limit and with 1 by the fused LayerNorm (fp16 operands only; the caller zeroes it).
+ * dtk_vit_gemm_split: the same roles on hi / lo planes (a, a_lo; w, w_lo = planes of w_scale * W; q .. vt_lo; out, out_lo); PROJ and
+ * FC2 add gamma * (A W^T + bias) to the fp32 stream x [rows][D] instead of storing an update. */
+#define DTK_VIT_GEMM_QKV 0
+#define DTK_VIT_GEMM_QKV_FACET 1
+#define DTK_VIT_GEMM_PROJ 2
+#define DTK_VIT_GEMM_FC1 3
+#define DTK_VIT_GEMM_FC2 4
+typedef struct dtk_vit_gemm_args {
+    int32_t role, D, flags, operand_type;
+    int64_t rows;
+    int32_t S, Sp;
+    float ln_eps, w_scale;
+    const void *a, *a_lo, *w, *w_lo;
+    const float *bias, *gamma;
+    void *q, *k, *vt, *q_lo, *k_lo, *vt_lo;
+    void *out, *out_lo;
+    float *out_f32, *x, *ln_x;
+    const float *ln_w, *ln_b;
+    void* ln_out;
+    int32_t* ovf;
+} dtk_vit_gemm_args;
+int dtk_vit_gemm(const dtk_vit_gemm_args* g, void* stream);
+int dtk_vit_gemm_split(const dtk_vit_gemm_args* g, void* stream);
+
 /* ---- P2: Delta-DINO refinement (models/tracker.py:113-135; models/networks/delta_dino.py:53-61;
  *      models/utils.py:7-45), fp32-grade on the fp16 MFMA (operands split into hi + lo halves, 3 products) ----------
  * dtk_delta_dino_pack: layer l in 0..3 (state-dict keys layers.{4l}.{weight,bias} = conv [Cout][Cin][5][5] and

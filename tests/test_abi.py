@@ -96,6 +96,43 @@ def test_adam_args_layout_matches_header():
     assert ctypes.sizeof(_lib.AdamArgs) == (4 * 8 + 8 + 4 + 4) * 32 + 4 + 4 + 4 * 8 + 3 * 8   # (4 bytes of padding in front of the doubles)
 
 
+def test_vit_gemm_args_layout_matches_header(handle):
+    """dtk_vit_gemm_args (the stand-alone GEMM stage): the ctypes mirror has the header's fields in the header's order, its size, and
+    the role constants are the header's; the entry points refuse what they cannot run without touching the device."""
+    import re
+    text = open(entry.os.path.join(entry.ROOT, "include", "dtk.h")).read()
+    body = re.search(r"typedef struct dtk_vit_gemm_args \{(.*?)\} dtk_vit_gemm_args;", text, flags=re.S).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    decls = re.findall(r"((?:const )?(?:void|float|int32_t|int64_t))\s*(\*?)\s*([^;]+);", body)
+    names, size = [], 0
+    for ctype, star, rest in decls:
+        for f in rest.split(","):
+            pointer = bool(star) or f.strip().startswith("*")
+            names.append(f.strip("* "))
+            width = 8 if pointer or ctype == "int64_t" else 4
+            assert size % width == 0, (names[-1], size)   # no padding anywhere: the mirror cannot drift by alignment
+            size += width
+    assert names == [n for n, _ in _lib.VitGemmArgs._fields_], names
+    assert ctypes.sizeof(_lib.VitGemmArgs) == size == 4 * 4 + 8 + 2 * 4 + 2 * 4 + 21 * 8
+    for i, (n, t) in enumerate(_lib.VitGemmArgs._fields_):
+        assert (ctypes.sizeof(t) == 8) == (n == "rows" or i >= 9), n
+    want = {"QKV": _lib.VIT_GEMM_QKV, "QKV_FACET": _lib.VIT_GEMM_QKV_FACET, "PROJ": _lib.VIT_GEMM_PROJ, "FC1": _lib.VIT_GEMM_FC1,
+            "FC2": _lib.VIT_GEMM_FC2}
+    for name, value in want.items():
+        m = re.search(rf"#define DTK_VIT_GEMM_{name} (\d+)", text)
+        assert m and int(m.group(1)) == value, name
+    assert sorted(want.values()) == list(range(5))
+    a = _lib.VitGemmArgs()
+    for fn in (handle.dtk_vit_gemm, handle.dtk_vit_gemm_split):
+        assert fn(None, None) == -1 and b"null pointer" in handle.dtk_last_error()
+        a.D = 512
+        assert fn(ctypes.byref(a), None) == -1 and b"D must be 384, 768 or 1024" in handle.dtk_last_error()
+        a.D, a.operand_type = 384, 7
+        assert fn(ctypes.byref(a), None) == -1 and b"operand_type" in handle.dtk_last_error()
+        a.operand_type, a.rows = 0, 0
+        assert fn(ctypes.byref(a), None) == -1 and b"rows" in handle.dtk_last_error()
+
+
 def test_m0_users(handle, tmp_path):
     """csrc/common.h dtk_buffer_lds16 writes m0 inside an asm statement the compiler cannot be told about (hipcc refuses
     reserved registers in clobber lists), so the rule is structural: a kernel that contains the descriptor form of LDS-DMA
