@@ -195,6 +195,14 @@ SIGNATURES = {
                                             c_void_p]),
     "dtk_batchnorm_train_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
                                              c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "dtk_pca_moments_workspace_bytes": (c_size_t, [ctypes.c_int64, c_int, ctypes.c_int64]),
+    "dtk_pca_moments": (c_int, [c_void_p, ctypes.c_int64, c_int, c_int, ctypes.c_int64, c_void_p, c_void_p, c_void_p, c_size_t,
+                                c_void_p]),
+    "dtk_pca_project_workspace_bytes": (c_size_t, [ctypes.c_int64]),
+    "dtk_pca_project": (c_int, [c_void_p, ctypes.c_int64, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
+                                c_void_p]),
+    "dtk_fg_mask": (c_int, [c_void_p, c_int, c_int, c_void_p, c_float, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                            c_void_p]),
 }
 
 _LIB = None

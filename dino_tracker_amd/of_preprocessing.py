@@ -16,9 +16,13 @@ outside the token grid) raise instead of wrapping an index silently.
 Command lines (the reference scripts' flags):
     python -m dino_tracker_amd.of_preprocessing split --traj_path T --fg_masks_path M --fg_traj_path F --bg_traj_path B
     python -m dino_tracker_amd.of_preprocessing of-filter --dino-bb-path P --traj-path T --out-path O [--dino-bb-stride 7 --h --w]
-    python -m dino_tracker_amd.of_preprocessing all --config config/preprocessing.yaml --data-path D
+    python -m dino_tracker_amd.of_preprocessing masks --config config/preprocessing.yaml --data-path D
+    python -m dino_tracker_amd.of_preprocessing all --config config/preprocessing.yaml --data-path D [--make-masks]
+`masks` writes the PCA foreground masks (dino_tracker_amd.fg_mask; main_preprocessing.py step 3) from the mask embedding file.
 `all` runs split, best-buddy extraction, optical-flow filter and NMS ratios (main_preprocessing.py step 4 and
-main_dino_bb_preprocessing.py steps 1, 3, 4) with the tensors on the device between steps, and writes the reference's files.
+main_dino_bb_preprocessing.py steps 1, 3, 4) with the tensors on the device between steps, and writes the reference's files.  With --make-masks it first builds the masks
+when the mask folder is missing -- from the mask embedding file if present, otherwise from the video; without the flag a missing
+mask folder is an error, as before.
 """
 from __future__ import annotations
 
@@ -163,7 +167,34 @@ def run_of_filter(dino_bb_path: str, traj_path: str, out_path: str, stride: int 
     return out
 
 
-def run_all(config_path: str, data_path: str, device="cuda:0"):
+def _load_config(config_path: str, data_path: str):
+    import yaml
+    from .utils import add_config_paths
+    with open(config_path) as fh:
+        return add_config_paths(data_path, yaml.safe_load(fh.read()))
+
+
+def run_masks(config_path: str, data_path: str, device="cuda:0", from_video: bool = False):
+    """main_preprocessing.py step 3 (create_fg_mask.py) on the reference's file layout: mask_dino_embed_video_path -> masks_path;
+    with `from_video` a missing embedding file is replaced by the video through the device encoder."""
+    from . import fg_mask
+    config = _load_config(config_path, data_path)
+    h, w, thr = config["video_resh"], config["video_resw"], config["fg_mask_threshold"]
+    emb_path = config["mask_dino_embed_video_path"]
+    if from_video and not os.path.exists(emb_path):
+        from .train import load_video
+        video = load_video(_need(config["video_folder"], "video frames"), resize=(h, w))
+        _, details = fg_mask.fg_masks_from_video(video, config["mask_dino_model_name"], config["mask_dino_layer"],
+                                                 config["mask_dino_stride"], img_size=(h, w), device=device,
+                                                 fg_mask_threshold=thr, return_details=True)
+        mask = details["mask"]
+        print(f"Saved fg. mask to {fg_mask.save_masks(mask, config['masks_path'])}")
+        return mask
+    _need(emb_path, "preprocessing/save_dino_embed_video.py")
+    return fg_mask.run(emb_path, h, w, config["masks_path"], fg_mask_threshold=thr, device=device)
+
+
+def run_all(config_path: str, data_path: str, device="cuda:0", make_masks: bool = False):
     """main_preprocessing.py step 4 + main_dino_bb_preprocessing.py steps 1, 3, 4 on the reference's file layout."""
     import yaml
     from .best_buddies import compute_bb_nms_all, extract_best_buddies
@@ -174,6 +205,8 @@ def run_all(config_path: str, data_path: str, device="cuda:0"):
     extract = "preprocessing/extract_trajectories.py"
     traj_path = _need(config["trajectories_file"], extract)
     unfiltered_path = _need(config["unfiltered_trajectories_file"], extract + " (without --filter-using-direct-flow)")
+    if make_masks and not os.path.exists(config["masks_path"]):
+        run_masks(config_path, data_path, device, from_video=True)
     masks_path = _need(config["masks_path"], "preprocessing/create_fg_mask.py")
     emb_path = _need(config["dino_embed_video_path"], "preprocessing/save_dino_embed_video.py")
     h, w, stride = config["video_resh"], config["video_resw"], config["dino_stride"]
@@ -201,8 +234,8 @@ def run_all(config_path: str, data_path: str, device="cuda:0"):
 
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
-    if not argv or argv[0] not in ("split", "of-filter", "all"):
-        raise SystemExit("usage: python -m dino_tracker_amd.of_preprocessing {split|of-filter|all} ...")
+    if not argv or argv[0] not in ("split", "of-filter", "masks", "all"):
+        raise SystemExit("usage: python -m dino_tracker_amd.of_preprocessing {split|of-filter|masks|all} ...")
     cmd, rest = argv[0], argv[1:]
     ap = argparse.ArgumentParser(prog=f"dino_tracker_amd.of_preprocessing {cmd}")
     if cmd == "split":   # preprocessing/split_trajectories_to_fg_bg.py
@@ -224,8 +257,13 @@ def main(argv=None):
     else:   # main_preprocessing.py / main_dino_bb_preprocessing.py
         ap.add_argument("--config", default="./config/preprocessing.yaml", type=str)
         ap.add_argument("--data-path", default="./dataset/libby", type=str)
+        if cmd == "masks":   # main_preprocessing.py step 3
+            a = ap.parse_args(rest)
+            run_masks(a.config, a.data_path)
+            return
+        ap.add_argument("--make-masks", action="store_true")
         a = ap.parse_args(rest)
-        run_all(a.config, a.data_path)
+        run_all(a.config, a.data_path, make_masks=a.make_masks)
 
 
 if __name__ == "__main__":

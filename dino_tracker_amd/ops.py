@@ -231,6 +231,60 @@ def of_filter_keep(traj: torch.Tensor, idx: torch.Tensor, gh: int, gw: int, orig
     return keep.bool(), err
 
 
+PCA_WIDTHS, PCA_MAX_Q = (384, 768, 1024), 8
+
+
+def _pca_rows(x: torch.Tensor) -> Tuple[int, int]:
+    if x.dim() < 2 or x.shape[-1] not in PCA_WIDTHS or x.numel() == 0:
+        raise RuntimeError(f"dino_tracker_amd: PCA input must be token-major [..., C] with C in {PCA_WIDTHS}, got {tuple(x.shape)}")
+    return x.numel() // x.shape[-1], int(x.shape[-1])
+
+
+def pca_moments(x: torch.Tensor, normalize: bool = True, chunk_rows: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """dtk_pca_moments: (mean [C], cov [C, C]) of the rows of a token-major fp32 volume [..., C]: cov is the centred Gram
+    sum_n (x^_n - mean)(x^_n - mean)^T of the F.normalize'd rows (raw rows when not `normalize`), not divided by the row count."""
+    N, C = _pca_rows(x)
+    mean = torch.empty(C, dtype=torch.float32, device=x.device)
+    cov = torch.empty((C, C), dtype=torch.float32, device=x.device)
+    nb = int(lib().dtk_pca_moments_workspace_bytes(N, C, int(chunk_rows)))
+    ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=x.device)
+    check(lib().dtk_pca_moments(_p(x, torch.float32), N, C, int(bool(normalize)), int(chunk_rows), _p(mean), _p(cov), _p(ws), nb,
+                                _stream()))
+    return mean, cov
+
+
+def pca_project(x: torch.Tensor, V: torch.Tensor, normalize: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
+    """dtk_pca_project: (colors [N, q], minmax [16]) -- the (normalised, uncentred) rows of x [..., C] on the q <= 8 rows of
+    V [q, C]; minmax[j] / minmax[8 + j] are the minimum / maximum of component j over all rows."""
+    N, C = _pca_rows(x)
+    if V.dim() != 2 or V.shape[1] != C or not 1 <= V.shape[0] <= PCA_MAX_Q:
+        raise RuntimeError(f"dino_tracker_amd: V must be [q <= {PCA_MAX_Q}, {C}], got {tuple(V.shape)}")
+    q = int(V.shape[0])
+    colors = torch.empty((N, q), dtype=torch.float32, device=x.device)
+    minmax = torch.empty(2 * PCA_MAX_Q, dtype=torch.float32, device=x.device)
+    nb = int(lib().dtk_pca_project_workspace_bytes(N))
+    ws = torch.empty(nb, dtype=torch.uint8, device=x.device)
+    check(lib().dtk_pca_project(_p(x, torch.float32), N, C, int(bool(normalize)), _p(V, torch.float32), q, _p(colors), _p(minmax),
+                                _p(ws), nb, _stream()))
+    return colors, minmax
+
+
+def fg_mask(colors: torch.Tensor, minmax: torch.Tensor, grid: Tuple[int, int, int], img_size: Tuple[int, int], threshold: float,
+            comp: int = 0, flip: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    """dtk_fg_mask: (mask [T, H, W], token mask [T, h, w]) uint8 0 / 255 from colors [T h w, q]: a token is foreground iff its
+    min-max normalised component `comp` (one minus it when `flip`) is below `threshold`; the mask is the nearest upsampling."""
+    T, h, w = (int(v) for v in grid)
+    H, W = (int(v) for v in img_size)
+    if colors.dim() != 2 or colors.shape[0] != T * h * w or minmax.shape != (2 * PCA_MAX_Q,):
+        raise RuntimeError(f"dino_tracker_amd: fg_mask: colors {tuple(colors.shape)} / minmax {tuple(minmax.shape)} do not fit "
+                           f"the grid {T}x{h}x{w}")
+    mask = torch.empty((T, H, W), dtype=torch.uint8, device=colors.device)
+    tok = torch.empty((T, h, w), dtype=torch.uint8, device=colors.device)
+    check(lib().dtk_fg_mask(_p(colors, torch.float32), int(colors.shape[1]), int(comp), _p(minmax, torch.float32), float(threshold),
+                            int(bool(flip)), T, h, w, H, W, _p(mask), _p(tok), _stream()))
+    return mask, tok
+
+
 def traj_cos_sims(S: torch.Tensor, tq: torch.Tensor, N: int, T: int) -> torch.Tensor:
     C = S.shape[-1]
     cs = torch.empty((N, T), dtype=torch.float32, device=S.device)

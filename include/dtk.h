@@ -596,6 +596,31 @@ int dtk_adam_step(const dtk_adam_args* a, void* stream);
 int dtk_adam_scalars(const dtk_adam_args* a, float* out_host);
 int dtk_adam_step_dev(const dtk_adam_args* a, const float* scalars_dev, void* stream);
 
+/* ---- PCA foreground masks (preprocessing/create_fg_mask.py:11-43) on a token-major fp32 volume x [N][C], C = 384, 768 or 1024 ----
+ * With `normalize` every row is x^_n = x_n / max(||x_n||, 1e-12) (F.normalize), otherwise x^_n = x_n.
+ *
+ * dtk_pca_moments: mean[C] = (1 / N) sum_n x^_n and cov[C][C] = sum_n (x^_n - mean)(x^_n - mean)^T (NOT divided by N), in two
+ * passes (mean first, then the centred Gram).  The Gram runs on the matrix cores on hi + lo fp16 planes of the centred values
+ * (three products, the lo.lo one dropped: 2^-21 relative to |Xc|^T |Xc| plus the fp32 accumulation); un-normalised input must
+ * stay inside the fp16 range after centring.  The tokens are split into chunks of `chunk_rows` (rounded up to a multiple of 32;
+ * 0 = the library's choice) whose partial sums are reduced in index order without atomics: two calls give the same bits, and
+ * cov is exactly symmetric.  Workspace: dtk_pca_moments_workspace_bytes(N, C, chunk_rows), 0 for arguments the call refuses.
+ *
+ * dtk_pca_project: colors[N][q] = x^_n . V[j] for V [q][C] (fp32, q <= 8; rows not centred, as the reference projects them) and
+ * minmax[16]: minmax[j] = min_n colors[n][j], minmax[8 + j] = the maximum (j < q; the rest +-inf).
+ *
+ * dtk_fg_mask: tmp = (colors[n][comp] - min) / (max - min), 1 - tmp when `flip`; token n = (t, y, x) of the [T][h][w] grid is
+ * foreground iff tmp < thr (max == min: never).  token_mask [T][h][w] and mask [T][H][W] are 0 / 255; mask is the nearest
+ * upsampling of F.interpolate: destination (y, x) reads token (floor(y h / H), floor(x w / W)). */
+size_t dtk_pca_moments_workspace_bytes(int64_t N, int32_t C, int64_t chunk_rows);
+int dtk_pca_moments(const float* x, int64_t N, int32_t C, int32_t normalize, int64_t chunk_rows, float* mean, float* cov,
+                    void* workspace, size_t workspace_bytes, void* stream);
+size_t dtk_pca_project_workspace_bytes(int64_t N);
+int dtk_pca_project(const float* x, int64_t N, int32_t C, int32_t normalize, const float* V, int32_t q, float* colors,
+                    float* minmax, void* workspace, size_t workspace_bytes, void* stream);
+int dtk_fg_mask(const float* colors, int32_t q, int32_t comp, const float* minmax, float thr, int32_t flip, int32_t T, int32_t h,
+                int32_t w, int32_t H, int32_t W, uint8_t* mask, uint8_t* token_mask, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
