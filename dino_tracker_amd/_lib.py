@@ -203,6 +203,12 @@ SIGNATURES = {
                                 c_void_p]),
     "dtk_fg_mask": (c_int, [c_void_p, c_int, c_int, c_void_p, c_float, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                             c_void_p]),
+    "dtk_flow_pack": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "dtk_flow_cycle_masks": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
+    "dtk_flow_traj_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "dtk_flow_traj_start": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p,
+                                    c_void_p, c_int, c_float, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "dtk_flow_traj_emit": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
 _LIB = None

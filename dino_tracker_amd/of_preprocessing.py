@@ -202,9 +202,9 @@ def run_all(config_path: str, data_path: str, device="cuda:0", make_masks: bool 
     from .utils import add_config_paths
     with open(config_path) as fh:
         config = add_config_paths(data_path, yaml.safe_load(fh.read()))
-    extract = "preprocessing/extract_trajectories.py"
-    traj_path = _need(config["trajectories_file"], extract)
-    unfiltered_path = _need(config["unfiltered_trajectories_file"], extract + " (without --filter-using-direct-flow)")
+    extract = "preprocessing/extract_trajectories.py (or python -m dino_tracker_amd.flow_trajectories)"
+    traj_path = _need(config["trajectories_file"], extract + " with --filter-using-direct-flow")
+    unfiltered_path = _need(config["unfiltered_trajectories_file"], extract + " without --filter-using-direct-flow")
     if make_masks and not os.path.exists(config["masks_path"]):
         run_masks(config_path, data_path, device, from_video=True)
     masks_path = _need(config["masks_path"], "preprocessing/create_fg_mask.py")

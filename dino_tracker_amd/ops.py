@@ -231,6 +231,69 @@ def of_filter_keep(traj: torch.Tensor, idx: torch.Tensor, gh: int, gw: int, orig
     return keep.bool(), err
 
 
+def flow_pack(flow: torch.Tensor) -> torch.Tensor:
+    """dtk_flow_pack: planar flow fields [n, 2, h, w] -> (x, y) pairs [n, h, w, 2]."""
+    if flow.dim() != 4 or flow.shape[1] != 2:
+        raise RuntimeError(f"dino_tracker_amd: flows must be [n, 2, h, w], got {tuple(flow.shape)}")
+    n, _, h, w = flow.shape
+    packed = torch.empty((n, h, w, 2), dtype=torch.float32, device=flow.device)
+    check(lib().dtk_flow_pack(_p(flow, torch.float32) if n else None, _p(packed) if n else None, n, h, w, _stream()))
+    return packed
+
+
+def _check_packed(fpk: torch.Tensor, bpk: torch.Tensor) -> Tuple[int, int, int]:
+    if fpk.dim() != 4 or fpk.shape[3] != 2 or bpk.shape != fpk.shape:
+        raise RuntimeError(f"dino_tracker_amd: packed flows must both be [T - 1, h, w, 2], got {tuple(fpk.shape)} and "
+                           f"{tuple(bpk.shape)}")
+    return int(fpk.shape[0]) + 1, int(fpk.shape[1]), int(fpk.shape[2])
+
+
+def flow_cycle_masks(fpk: torch.Tensor, bpk: torch.Tensor, threshold: float) -> torch.Tensor:
+    """dtk_flow_cycle_masks on packed flows: consistent [T, h, w] uint8 (0 / 1)."""
+    T, h, w = _check_packed(fpk, bpk)
+    out = torch.empty((T, h, w), dtype=torch.uint8, device=fpk.device)
+    check(lib().dtk_flow_cycle_masks(_p(fpk, torch.float32), _p(bpk, torch.float32), T, h, w, float(threshold), _p(out), _stream()))
+    return out
+
+
+def flow_traj_workspace(T: int, h: int, w: int, device) -> torch.Tensor:
+    nb = int(lib().dtk_flow_traj_workspace_bytes(T, h, w))
+    if nb == 0:
+        raise RuntimeError(f"dino_tracker_amd: flow trajectories need T >= 2 and h, w >= 2, got T={T} {h}x{w}")
+    return torch.empty(nb, dtype=torch.uint8, device=device)
+
+
+def flow_traj_start(fpk: torch.Tensor, bpk: torch.Tensor, consistent: torch.Tensor, visited: torch.Tensor, s: int, threshold: float,
+                    min_trajectory_length: int, ws: torch.Tensor, n_rows: torch.Tensor,
+                    direct: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, direct_threshold: Optional[float] = None) -> None:
+    """dtk_flow_traj_start for the starting frame s; `n_rows` [1] int32 on the device receives the kept-row count.  `direct`:
+    packed (forward, backward) flows s -> s + k + 1 [T - 1 - s, h, w, 2], together with `direct_threshold`."""
+    T, h, w = _check_packed(fpk, bpk)
+    if consistent.shape != (T, h, w) or visited.shape != (T, h, w):
+        raise RuntimeError(f"dino_tracker_amd: consistent / visited must be [{T}, {h}, {w}]")
+    use_direct = direct_threshold is not None
+    df = db = None
+    if direct is not None and T - 1 - s > 0:
+        df, db = direct
+        if df.shape != (T - 1 - s, h, w, 2) or db.shape != df.shape:
+            raise RuntimeError(f"dino_tracker_amd: direct flows of start {s} must be [{T - 1 - s}, {h}, {w}, 2], got "
+                               f"{tuple(df.shape)} and {tuple(db.shape)}")
+    check(lib().dtk_flow_traj_start(_p(fpk, torch.float32), _p(bpk, torch.float32), _p(consistent, torch.uint8),
+                                    _p(visited, torch.uint8), T, h, w, int(s), float(threshold), int(min_trajectory_length),
+                                    _p(df, torch.float32), _p(db, torch.float32), int(use_direct),
+                                    float(direct_threshold) if use_direct else 0.0, _p(n_rows, torch.int32), _p(ws),
+                                    ws.numel(), _stream()))
+
+
+def flow_traj_emit(T: int, h: int, w: int, s: int, min_trajectory_length: int, n_rows: int, visited: torch.Tensor,
+                   ws: torch.Tensor) -> torch.Tensor:
+    """dtk_flow_traj_emit: the rows [n_rows, T, 2] of the walk dtk_flow_traj_start left in `ws`; marks `visited`."""
+    rows = torch.empty((n_rows, T, 2), dtype=torch.float32, device=ws.device)
+    check(lib().dtk_flow_traj_emit(T, h, w, int(s), int(min_trajectory_length), int(n_rows), _p(rows) if n_rows else None,
+                                   _p(visited, torch.uint8), _p(ws), ws.numel(), _stream()))
+    return rows
+
+
 PCA_WIDTHS, PCA_MAX_Q = (384, 768, 1024), 8
 
 

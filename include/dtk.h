@@ -621,6 +621,45 @@ int dtk_pca_project(const float* x, int64_t N, int32_t C, int32_t normalize, con
 int dtk_fg_mask(const float* colors, int32_t q, int32_t comp, const float* minmax, float thr, int32_t flip, int32_t T, int32_t h,
                 int32_t w, int32_t H, int32_t W, uint8_t* mask, uint8_t* token_mask, void* stream);
 
+/* ---- Trajectories chained from optical flow (preprocessing/extract_trajectories.py:75-93, :143-158, :203-266: everything behind
+ * the RAFT network) ----------------------------------------------------------------------------------------------------------------
+ * Flows are fp32 pixel displacements; fflow[i] maps frame i -> i + 1 and bflow[i] frame i + 1 -> i (the reference's flows[0] and
+ * flows[1]).  dtk_flow_pack turns n planar fields [n][2][h][w] into the PACKED form [n][h][w][2] every other entry reads.
+ *
+ * The arithmetic is the specification.  Positions are fp32 and every step is one IEEE-754 operation, never contracted, with
+ * correctly rounded division and square root.  A bilinear read at (x, y) is grid_sample(align_corners=True) written out:
+ *   gx = 2 x / (w - 1) - 1;  ix = ((gx + 1) / 2) (w - 1)  (y alike);  x0 = floor(ix), x1 = x0 + 1;
+ *   weights (x1 - ix)(y1 - iy), (ix - x0)(y1 - iy), (x1 - ix)(iy - y0), (ix - x0)(iy - y0) for the corners (x0, y0), (x1, y0),
+ *   (x0, y1), (x1, y1), the four products summed in that order from zero; a corner outside the image contributes zero.
+ * "Border padding" clamps ix, iy to the image before the floor.  A distance is sqrt(dx dx + dy dy).  round() is half to even.
+ *
+ * dtk_flow_cycle_masks: consistent [T][h][w] (0 / 1).  consistent[0] = 0; for pixel g of frame i + 1, c = g + bflow[i](g),
+ *   c' = c + bilinear(fflow[i], c): consistent[i + 1](g) = |g - c'| < threshold AND g = round(p + fflow[i](p)) for some pixel p.
+ *
+ * dtk_flow_traj_start, for the starting frame s (call s = 0, 1, ... in order on one stream; `visited` [T][h][w] starts zeroed):
+ *   a pixel is live when consistent[s] is 0 there or visited[s] is 0 there; the live pixels, in raster order, walk
+ *     x' = x + bilinear(fflow[s + k], x);  err = |x - (x' + bilinear(bflow[s + k], x'))|      k = 0 .. T - 2 - s
+ *   and stay live while err < threshold and x' lies in [0, w - 1] x [0, h - 1]; the run ends at the first dead step.  With
+ *   use_direct (direct_fwd / direct_back: packed [T - 1 - s][h][w][2], the flows s -> s + k + 1 and back) additionally
+ *     d = start + direct_fwd[k](start);  dmask = |start - (d + bilinear_border(direct_back[k], d))| < threshold and d inside;
+ *     the point stays live only while |x' - d| dmask < direct_threshold.
+ *   *n_rows (device) receives the number of runs of at least min_trajectory_length frames.  No host synchronisation.
+ * dtk_flow_traj_emit, with the same workspace and n_rows read back by the caller: rows [n_rows][T][2], the kept runs in raster
+ *   order, NaN outside frames s .. s + length - 1; every point of a kept run sets visited[frame][round(y)][round(x)].
+ * The blocks of s = 0, 1, ... concatenated are the reference's rows in the reference's order.
+ * Workspace: dtk_flow_traj_workspace_bytes(T, h, w) (a [T][h w] slab of points and the compaction lists), 0 for sizes the calls
+ * refuse (T < 2, h or w < 2). */
+int dtk_flow_pack(const float* flow, float* packed, int32_t n, int32_t h, int32_t w, void* stream);
+int dtk_flow_cycle_masks(const float* fflow_packed, const float* bflow_packed, int32_t T, int32_t h, int32_t w, float threshold,
+                         uint8_t* consistent, void* stream);
+size_t dtk_flow_traj_workspace_bytes(int32_t T, int32_t h, int32_t w);
+int dtk_flow_traj_start(const float* fflow_packed, const float* bflow_packed, const uint8_t* consistent, const uint8_t* visited,
+                        int32_t T, int32_t h, int32_t w, int32_t s, float threshold, int32_t min_trajectory_length,
+                        const float* direct_fwd, const float* direct_back, int32_t use_direct, float direct_threshold,
+                        int32_t* n_rows, void* workspace, size_t workspace_bytes, void* stream);
+int dtk_flow_traj_emit(int32_t T, int32_t h, int32_t w, int32_t s, int32_t min_trajectory_length, int32_t n_rows, float* rows,
+                       uint8_t* visited, const void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
