@@ -17,6 +17,10 @@ namespace {
 
 constexpr int TM = 64, TN = 64, TK = 16;
 constexpr int HR = 6;  // output rows per conv block in head_exact_kernel
+// Token grids whose map, logits and hidden ring do not fit 160 KiB of LDS together (128 x 128, the 101 x 181 of a 720 x 1280 video)
+// take head_exact_kernel<true>: the map is read from global memory (the workspace chunk, cache-resident) instead of an LDS copy and
+// the hidden ring holds HR_LARGE output rows per block.  Every cell sees the same operations in the same order in both forms.
+constexpr int HR_LARGE = 2;
 
 // ---- head parameter packing: W / sum(W) per (out,in) kernel, conv_norm.py:34-46 ---------------------------
 __global__ void head_prepare_kernel(const float* __restrict__ w1, const float* __restrict__ b1,
@@ -179,6 +183,7 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
 
 namespace {
 
+template <bool LARGE>
 __global__ __launch_bounds__(256) void head_exact_kernel(dtk_geom g, const float* __restrict__ head,
                                                          const float* __restrict__ maps, int HWs,
                                                          const int32_t* __restrict__ out_idx,
@@ -188,17 +193,21 @@ __global__ __launch_bounds__(256) void head_exact_kernel(dtk_geom g, const float
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int HW = g.ph * g.pw, pw = g.pw, ph = g.ph;
     const int HWp = (HW + 3) & ~3;
-    float* sx = smem;                 // relu'd cosine map
-    float* sz = sx + HWp;             // refined logits
-    float* sh = sz + HWp;             // hidden ring [16][HR+2][pw]
-    float* red = sh + DTK_HEAD_HIDDEN * (HR + 2) * pw;  // 16 floats
+    constexpr int HRK = LARGE ? HR_LARGE : HR;
+    float* sz = LARGE ? smem : smem + HWp;   // refined logits (behind the LDS copy of the map, where there is one)
+    float* sh = sz + HWp;             // hidden ring [16][HRK+2][pw]
+    float* red = sh + DTK_HEAD_HIDDEN * (HRK + 2) * pw;  // 16 floats
     int* redi = reinterpret_cast<int*>(red + 8);
     const int i = blockIdx.x;
     const int m = m0 + i;
     if (i >= count || m >= dtk_active(M, dM)) return;
     const int tid = threadIdx.x;
     const float* map = maps + (size_t)i * HWs;
-    for (int c = tid; c < HW; c += 256) sx[c] = map[c];
+    const float* sx = map;            // relu'd cosine map: in LDS unless LARGE
+    if constexpr (!LARGE) {
+        for (int c = tid; c < HW; c += 256) smem[c] = map[c];
+        sx = smem;
+    }
     __syncthreads();
 
     // first maximum (torch.argmax): larger value wins, ties -> lower flat index
@@ -227,9 +236,9 @@ __global__ __launch_bounds__(256) void head_exact_kernel(dtk_geom g, const float
     const float* b1 = head + 144;        // [16]
     const float* w2 = head + 160;        // [16][9]
     const float b2 = head[304];
-    const int ring = HR + 2;
-    for (int r0 = 0; r0 < ph; r0 += HR) {
-        const int nout = min(HR, ph - r0);
+    const int ring = HRK + 2;
+    for (int r0 = 0; r0 < ph; r0 += HRK) {
+        const int nout = min(HRK, ph - r0);
         // hidden rows r0-1 .. r0+nout (zero outside the map: conv2's zero padding)
         for (int idx = tid; idx < (nout + 2) * pw; idx += 256) {
             const int hr = idx / pw, c = idx - hr * pw;
@@ -345,10 +354,34 @@ extern "C" int dtk_head_forward(const dtk_geom* g, const float* head, const floa
 
 // ---- host driver of the exact path -----------------------------------------------------------------------
 static inline int exact_hws(const dtk_geom* g) { return (g->ph * g->pw + 63) & ~63; }
-static inline size_t exact_head_lds(const dtk_geom* g) {
+static inline size_t exact_head_lds(const dtk_geom* g, bool large) {
     const int HWp = (g->ph * g->pw + 3) & ~3;
-    return sizeof(float) * (size_t)(2 * HWp + DTK_HEAD_HIDDEN * (HR + 2) * g->pw + 16);
+    return sizeof(float) * (size_t)((large ? 1 : 2) * HWp + DTK_HEAD_HIDDEN * ((large ? HR_LARGE : HR) + 2) * g->pw + 16);
 }
+constexpr size_t EXACT_LDS_MAX = 160 * 1024;
+// head_exact_kernel on `cnt` maps: the form with the map in LDS where it fits, the large-grid form where only that one fits,
+// DTK_E_INVALID beyond (ph * pw + 64 * pw + 16 floats > 160 KiB; dtk.h)
+static int launch_head_exact(const char* who, const char* name, const dtk_geom* g, const float* head, const float* maps, int HWs,
+                             const int32_t* out_idx, float* out_xy, int m0, int cnt, int M, const int32_t* dM, int normalized,
+                             float* stats, hipStream_t st) {
+    const bool large = exact_head_lds(g, false) > EXACT_LDS_MAX;
+    const size_t lds = exact_head_lds(g, large);
+    DTK_REQUIRE(lds <= EXACT_LDS_MAX, "%s: token grid %dx%d needs %zu B of LDS (> 160 KiB)", who, g->ph, g->pw, lds);
+    if (large) {
+        DTK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(head_exact_kernel<true>),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        DTK_LAUNCH(name, head_exact_kernel<true>, dim3(cnt), dim3(256), lds, st, *g, head, maps, HWs, out_idx, out_xy, m0, cnt, M,
+                   dM, normalized, stats);
+    } else {
+        DTK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(head_exact_kernel<false>),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        DTK_LAUNCH(name, head_exact_kernel<false>, dim3(cnt), dim3(256), lds, st, *g, head, maps, HWs, out_idx, out_xy, m0, cnt, M,
+                   dM, normalized, stats);
+    }
+    return DTK_OK;
+}
+// whether the exact path serves this token grid (the MFMA path asks before it starts: its third tier is this path)
+bool dtk_track_exact_fits(const dtk_geom* g) { return exact_head_lds(g, true) <= EXACT_LDS_MAX; }   // (the smaller of the two forms)
 constexpr int EXACT_CHUNK = 4096;  // 4096 maps x 32 KB = 133 MB: stays in the 256 MiB Infinity Cache
 
 size_t dtk_track_exact_workspace_bytes(const dtk_geom* g, int M) {
@@ -361,8 +394,8 @@ int dtk_track_exact(const dtk_geom* g, const float* feat, const float* norms, co
                     const int32_t* dM, int normalized, void* workspace, size_t workspace_bytes, void* stream) {
     DTK_REQUIRE(g->C % TK == 0, "dtk_track(exact): C=%d must be a multiple of %d", g->C, TK);
     const int HWs = exact_hws(g);
-    const size_t lds = exact_head_lds(g);
-    DTK_REQUIRE(lds <= 160 * 1024, "dtk_track(exact): token grid %dx%d needs %zu B of LDS (> 160 KiB)", g->ph, g->pw, lds);
+    DTK_REQUIRE(dtk_track_exact_fits(g), "dtk_track(exact): token grid %dx%d needs %zu B of LDS (> 160 KiB)", g->ph, g->pw,
+                exact_head_lds(g, true));
     long long chunk = (long long)(workspace_bytes / ((size_t)(HWs + 1) * sizeof(float)));
     if (chunk > M) chunk = M;
     if (chunk > 65535LL * TM) chunk = 65535LL * TM;
@@ -372,8 +405,6 @@ int dtk_track_exact(const dtk_geom* g, const float* feat, const float* norms, co
         return DTK_E_WORKSPACE;
     }
     hipStream_t st = dtk_stream(stream);
-    DTK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(head_exact_kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     float* maps = reinterpret_cast<float*>(workspace);
     float* snorm = maps + (size_t)chunk * HWs;
     const int HW = g->ph * g->pw;
@@ -383,8 +414,9 @@ int dtk_track_exact(const dtk_geom* g, const float* feat, const float* norms, co
                            cnt, M, dM, g->C);
         DTK_LAUNCH("corr_exact", corr_exact_kernel, dim3(dtk_cdiv(HW, TN), dtk_cdiv(cnt, TM)), dim3(256), 0, st, *g, feat,
                            norms, emb, src_row, tgt, snorm, maps, (int)m0, cnt, M, dM, HWs, 1);
-        DTK_LAUNCH("head_exact", head_exact_kernel, dim3(cnt), dim3(256), lds, st, *g, head, maps, HWs, out_idx, out_xy,
-                           (int)m0, cnt, M, dM, normalized, (float*)nullptr);
+        const int rc = launch_head_exact("dtk_track(exact)", "head_exact", g, head, maps, HWs, out_idx, out_xy, (int)m0, cnt, M, dM,
+                                         normalized, nullptr, st);
+        if (rc) return rc;
     }
     return DTK_OK;
 }
@@ -394,13 +426,8 @@ extern "C" int dtk_head_forward(const dtk_geom* g, const float* head, const floa
     DTK_REQUIRE(g && head && maps && out_xy && B >= 0, "dtk_head_forward: null pointer");
     DTK_REQUIRE(g->ph > 0 && g->pw > 0 && g->stride > 0 && g->patch > 0, "dtk_head_forward: bad geometry");
     if (B == 0) return DTK_OK;
-    const size_t lds = exact_head_lds(g);
-    DTK_REQUIRE(lds <= 160 * 1024, "dtk_head_forward: token grid %dx%d needs %zu B of LDS (> 160 KiB)", g->ph, g->pw, lds);
-    DTK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(head_exact_kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    DTK_LAUNCH("head_exact", head_exact_kernel, dim3(B), dim3(256), lds, dtk_stream(stream), *g, head, maps, g->ph * g->pw,
-                       (const int32_t*)nullptr, out_xy, 0, B, B, (const int32_t*)nullptr, normalized, (float*)nullptr);
-    return DTK_OK;
+    return launch_head_exact("dtk_head_forward", "head_exact", g, head, maps, g->ph * g->pw, nullptr, out_xy, 0, B, B, nullptr,
+                             normalized, nullptr, dtk_stream(stream));
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -709,13 +736,8 @@ extern "C" int dtk_head_forward_train(const dtk_geom* g, const float* head, cons
     DTK_REQUIRE(g && head && maps && out_xy && stats && B >= 0, "dtk_head_forward_train: null pointer");
     DTK_REQUIRE(g->ph > 0 && g->pw > 0 && g->stride > 0 && g->patch > 0, "dtk_head_forward_train: bad geometry");
     if (B == 0) return DTK_OK;
-    const size_t lds = exact_head_lds(g);
-    DTK_REQUIRE(lds <= 160 * 1024, "dtk_head_forward_train: token grid %dx%d needs %zu B of LDS (> 160 KiB)", g->ph, g->pw, lds);
-    DTK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(head_exact_kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    DTK_LAUNCH("train_head_fwd", head_exact_kernel, dim3(B), dim3(256), lds, dtk_stream(stream), *g, head, maps, g->ph * g->pw,
-               (const int32_t*)nullptr, out_xy, 0, B, B, (const int32_t*)nullptr, normalized, stats);
-    return DTK_OK;
+    return launch_head_exact("dtk_head_forward_train", "train_head_fwd", g, head, maps, g->ph * g->pw, nullptr, out_xy, 0, B, B,
+                             nullptr, normalized, stats, dtk_stream(stream));
 }
 
 extern "C" int dtk_head_backward(const dtk_geom* g, const float* head, const float* maps, const float* stats, const float* grad_out,

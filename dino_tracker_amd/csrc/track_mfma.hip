@@ -30,6 +30,7 @@ int dtk_track_exact(const dtk_geom* g, const float* feat, const float* norms, co
                     const int32_t* src_row, const int32_t* tgt, const int32_t* out_idx, float* out_xy, int M,
                     const int32_t* dM, int normalized, void* workspace, size_t workspace_bytes, void* stream);
 size_t dtk_track_exact_workspace_bytes(const dtk_geom* g, int M);
+bool dtk_track_exact_fits(const dtk_geom* g);
 
 namespace {
 
@@ -2438,6 +2439,8 @@ int dtk_track_mfma(const dtk_geom* g, const float* feat, const float* norms, con
     const int ph = g->ph, pw = g->pw;
     const size_t lds_head = (size_t)((((ph + 2) * map_xw(pw) + 32 + 7) & ~7)) * 2 + 64 + 16 * 4 + (1 + KC) * 4 + 16;
     DTK_REQUIRE(lds_head <= 160 * 1024, "dtk_track(mfma): token grid %dx%d too large for head16 (%zu B LDS)", ph, pw, lds_head);
+    // (tier 3 is the exact path: refuse up front what it cannot serve, not when the first source happens to need it)
+    DTK_REQUIRE(dtk_track_exact_fits(g), "dtk_track(mfma): token grid %dx%d too large for the exact tier (160 KiB of LDS)", ph, pw);
     DTK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(head16_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)lds_head));
     DTK_HIP(hipMemsetAsync(counters, 0, 4 * sizeof(int32_t), st));

@@ -367,6 +367,10 @@ int dtk_corr_maps(const dtk_geom* g, const float* feat, const float* norms, cons
  *                 The workspace size follows it.  Results do not depend on it (tests run several rounds with it).
  * opts->tier: DTK_TIER_AUTO, or DTK_TIER_WHOLE_MAP = skip the certificate, every source takes tier 2 (tests).
  * `dM` (device int32*, may be NULL): if given, the number of sources is min(M, *dM).
+ * Token grid: both methods (and dtk_head_forward / dtk_head_forward_train) keep one map's logits and a ring of hidden rows in LDS,
+ *                 so they serve grids with  ph * pw + 64 * pw + 16 <= 40 960  floats (160 KiB) -- 101 x 181 (720 x 1280) and
+ *                 128 x 128 are inside, 153 x 273 (1080 x 1920) is not -- and return DTK_E_INVALID with a message beyond, before
+ *                 any source is processed.  (Up to 2 * ph * pw + 128 * pw + 16 <= 40 960 the map itself sits in LDS as well.)
  * `stats` (HOST pointer, may be NULL): filled before returning; nothing is retained by the library between calls. */
 #define DTK_TRACK_EXACT 0
 #define DTK_TRACK_MFMA 1

@@ -96,6 +96,39 @@ def test_refine_vs_oracle(C, H, W):
     assert (norms.cpu() - ref.norm(dim=1).reshape(T, -1)).abs().max() < 1e-4
 
 
+@pytest.mark.parametrize("C,H,W", [(32, 99, 127), (32, 101, 131), (32, 143, 211), (32, 57, 71), (32, 119, 245), (384, 101, 131)])
+def test_refine_odd_sizes_vs_oracle(C, H, W):
+    """Frame sizes that are odd in both dimensions and, but for 119 x 245, no multiple of 7 (every other size of this file is even
+    and, apart from 476, a multiple of 7): odd extents through the three BlurPools (99 -> 50 -> 25 -> 13), (H - 14) // 7 flooring in
+    the token grid, and the alignment of a CNN map whose last cell lies short of the frame edge.  Split mode within FEAT_TOL, fp16 operands within 2e-3
+    of the residual's size, norms within 1e-4 -- the bounds of the two tests above."""
+    from gpu_util import make_tracker
+    T = 2
+    ph, pw = A.feature_grid(H, W)
+    assert H % 2 == 1 and W % 2 == 1
+    video = synth.synth_video(T, H, W, seed=61)
+    dino = synth.synth_features(T, C, ph, pw, seed=62)
+    delta = synth.synth_delta_dino_weights(C, seed=63)
+    ref = A.refine_features(video, dino, delta)
+    res_scale = float((ref - dino).abs().max())
+    got = {}
+    for mode in ("split", "fp16"):
+        trk = make_tracker(video, dino, synth.synth_head_weights(3), delta=delta, p2_operands=mode)
+        trk.eval()
+        trk.cache_refined_embeddings()
+        got[mode] = trk.refined_features.cpu()
+        if mode == "split":
+            _, norms, _ = trk.features()
+            nerr = float((norms.cpu() - ref.norm(dim=1).reshape(T, -1)).abs().max())
+    err_split, err16 = float((got["split"] - ref).abs().max()), float((got["fp16"] - ref).abs().max())
+    print(f"C={C} {H}x{W} ({ph}x{pw}): residual scale {res_scale:.3g}, split {err_split:.3g}, fp16 operands {err16:.3g} "
+          f"({err16 / res_scale:.2g} of the residual), norms {nerr:.3g}")
+    assert got["split"].shape == ref.shape and torch.isfinite(got["split"]).all() and torch.isfinite(got["fp16"]).all()
+    assert err_split < FEAT_TOL
+    assert err16 < 2e-3 * res_scale
+    assert nerr < 1e-4
+
+
 def test_training_mode_is_refused():
     from gpu_util import make_tracker
     cfg = MG.CASES["p23_small"]
