@@ -121,6 +121,7 @@ __global__ __launch_bounds__(256) void conv5x5_kernel(const float* __restrict__ 
 // ---------------------------------------------------------------------------------------------------------------
 typedef _Float16 half_t;
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+typedef _Float16 h2v __attribute__((ext_vector_type(2)));
 constexpr int SK = 16;             // cin per chunk
 constexpr int SPT = 24;            // LDS pitch of one 16-cin row in halves (48 B)
 constexpr int STY = 16, STX = 16;  // pixel tile
@@ -310,6 +311,139 @@ __global__ __launch_bounds__(256, 3) void conv5x5_split_kernel(const half_t* __r
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// fp16 forward convolution of layers 2-4 for DTK_DD_FP16 (inference only; the training operators and DTK_DD_FP16_V1 stay on
+// conv5x5_split_kernel<.., SINGLE = true>).  Same operands, same products and the same accumulation chain per output --
+// 32x32x16 f16 MFMAs over 16-cin chunks in the order ck, ky, kx -- so the results are the bits of the SINGLE kernel.
+// What differs is how the operands reach the matrix unit:
+//   * LDS rows stay dense (32 B per pixel / per cout) but the two 16-byte pieces of a row are swapped on alternate rows
+//     (x: by the patch row's parity, w: by bit 3 of the cout row).  With a patch pitch of 4 or 0 mod 8 pixels every 16-lane
+//     group of a ds_read_b128 fragment read then covers 16 distinct 16-byte slots of the 256-byte bank row: conflict-free
+//     at the LDS size of the dense layout.
+//   * N-tile n, column j is output channel 2j + n (the tap row is de-interleaved as it is written to LDS), so a lane holds
+//     the channel pair (2 li, 2 li + 1) of a pixel and half a wave stores one whole 128-byte line (fp16; two lines in fp32)
+//     per instruction -- half the store instructions of the 2-byte form.
+// Workgroup = 16 x 16 pixels x 64 cout, wave = 4 x 16 pixels (2 x 2 accumulator tiles), two barriers per tap row as before.
+// Measured one at a time (docs/KERNELS.md, ablation table): the stores are most of the gain, the conflict-free reads 1 %;
+// double-buffered weights (one barrier per tap row) and a 4 x 2 wave tile bought nothing and are not here.
+// Resources (gfx950 code object), designed for four workgroups per CU = four waves per SIMD (the VGPR limit; LDS would
+// allow five): dilation 1: 23 040 B LDS (x 12 800 + w 10 240), 122 VGPRs;  dilation 2: 28 672 B (x 18 432), 128 VGPRs;
+// no scratch, no spills.
+// ---------------------------------------------------------------------------------------------------------------
+template <int DIL>
+struct HalfCfg {
+    static constexpr int PY = STY + 4 * DIL, PX = STX + 4 * DIL;   // 20 (4 mod 8) or 24 (0 mod 8) pixels
+    static constexpr int X_HALVES = PY * PX * SK;
+    static constexpr int W_HALVES = 5 * 64 * SK;                   // one tap row
+    static constexpr size_t LDS_BYTES = (size_t)(X_HALVES + W_HALVES) * sizeof(half_t);
+    static_assert(PX % 8 == 0 || PX % 8 == 4, "the piece swap by row parity needs a pitch of 0 or 4 mod 8 pixels");
+};
+
+template <int DIL, bool OUT_F32>
+__global__ __launch_bounds__(256, 4) void conv5x5_half_kernel(const half_t* __restrict__ in, const half_t* __restrict__ Wh,
+                                                              const float* __restrict__ scale, const float* __restrict__ shift,
+                                                              half_t* __restrict__ out16, float* __restrict__ out32, int H, int W,
+                                                              int Cin, int Cout, int relu, int tiles_x) {
+    typedef HalfCfg<DIL> Cfg;
+    constexpr int PY = Cfg::PY, PX = Cfg::PX;
+    extern __shared__ __attribute__((aligned(16))) half_t smem_h[];
+    half_t* Xs = smem_h;                   // [PY][PX][16], pieces swapped on odd rows
+    half_t* Wb = Xs + Cfg::X_HALVES;       // [5 taps][64 cout, even channels first][16], pieces swapped where row & 8
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int ct = blockIdx.y;
+    const size_t frame = blockIdx.z;
+    const int ty = blockIdx.x / tiles_x, tx = blockIdx.x % tiles_x;
+    const int y0 = ty * STY, x0 = tx * STX;
+    const half_t* fin = in + frame * (size_t)H * W * Cin;
+    const int li = lane & 31, hi = lane >> 5;
+    const int ly = w * 4 + (li >> 3), lx = li & 7;   // M-tile m covers columns m*8 .. m*8+7 of the wave's 4 rows
+    const int nck = Cin / SK;
+    f16v acc[2][2];
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int n = 0; n < 2; ++n)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[m][n][r] = 0.f;
+    // a tap row = 5 taps x 64 cout x 2 pieces of 16 bytes = 640 pieces: three per thread (the third for tid < 128), through
+    // registers one stage ahead.  Piece q = (tap, cout c, half): LDS row tap * 64 + (c & 1) * 32 + (c >> 1).
+    uint4 wr0, wr1, wr2;
+    // (pieces tid + 256 and tid + 512 are the same cout two and four taps on)
+    const int wrow = tid >> 1, wcd = (wrow & 1) * 32 + ((wrow & 63) >> 1);
+    const int wdst = ((wrow & ~63) + wcd) * SK + (((tid & 1) ^ ((wcd >> 3) & 1)) * 8);
+    const half_t* wsrc = Wh + (size_t)ct * nck * 25 * 64 * SK + (size_t)tid * 8;
+#define DDH_WLOAD(it_)                                                                          \
+    do {                                                                                        \
+        const half_t* s_ = wsrc + (size_t)(it_) * (5 * 64 * SK);                                \
+        wr0 = *reinterpret_cast<const uint4*>(s_);                                              \
+        wr1 = *reinterpret_cast<const uint4*>(s_ + 256 * 8);                                    \
+        if (tid < 128) wr2 = *reinterpret_cast<const uint4*>(s_ + 512 * 8);                     \
+    } while (0)
+    DDH_WLOAD(0);
+    const int wrd = li * SK + ((hi ^ ((li >> 3) & 1)) * 8);   // this lane's B fragment inside (tap, N-tile)
+    for (int ck = 0; ck < nck; ++ck) {
+        __syncthreads();   // the previous chunk's last tap row has been read
+        for (int idx = tid; idx < PY * PX * 2; idx += 256) {
+            const int piece = idx & 1, p = idx >> 1;
+            const int py = p / PX, px = p - py * PX;
+            const int gy = reflect(y0 - 2 * DIL + py, H), gx = reflect(x0 - 2 * DIL + px, W);
+            const uint4 v = *reinterpret_cast<const uint4*>(fin + ((size_t)gy * W + gx) * Cin + ck * SK + piece * 8);
+            *reinterpret_cast<uint4*>(Xs + p * SK + ((piece ^ (py & 1)) * 8)) = v;
+        }
+        for (int ky = 0; ky < 5; ++ky) {
+            const int it = ck * 5 + ky;     // tap rows are contiguous in the packed weights: [ct][ck][25 taps][64][16]
+            if (ky) __syncthreads();   // the previous tap row has been read
+            *reinterpret_cast<uint4*>(Wb + wdst) = wr0;
+            *reinterpret_cast<uint4*>(Wb + wdst + 128 * SK) = wr1;
+            if (tid < 128) *reinterpret_cast<uint4*>(Wb + wdst + 256 * SK) = wr2;
+            __syncthreads();
+            if (it + 1 < nck * 5) DDH_WLOAD(it + 1);
+            const int prow = ly + ky * DIL;
+            const half_t* xrow = Xs + (prow * PX + lx) * SK + ((hi ^ (prow & 1)) * 8);
+#pragma unroll
+            for (int kx = 0; kx < 5; ++kx) {
+                h8 xf[2], wf[2];
+#pragma unroll
+                for (int m = 0; m < 2; ++m) xf[m] = *reinterpret_cast<const h8*>(xrow + (m * 8 + kx * DIL) * SK);
+#pragma unroll
+                for (int n = 0; n < 2; ++n) wf[n] = *reinterpret_cast<const h8*>(Wb + (kx * 64 + n * 32) * SK + wrd);
+#pragma unroll
+                for (int n = 0; n < 2; ++n)
+#pragma unroll
+                    for (int m = 0; m < 2; ++m)
+                        acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(xf[m], wf[n], acc[m][n], 0, 0, 0);
+            }
+        }
+    }
+#undef DDH_WLOAD
+    // D[i][j]: j = li -> channels 2 li (n = 0) and 2 li + 1 (n = 1); i = (r&3) + 8*(r>>2) + 4*hi (pixel of the 4 x 8 block)
+    const int co = ct * 64 + 2 * li;
+    if (co >= Cout) return;   // Cout is even
+    const float sc0 = scale[co], sh0 = shift[co], sc1 = scale[co + 1], sh1 = shift[co + 1];
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int i = (r & 3) + 8 * (r >> 2) + 4 * hi;
+            const int oy = y0 + w * 4 + (i >> 3), ox = x0 + m * 8 + (i & 7);
+            if (oy < H && ox < W) {
+                float v0 = (acc[m][0][r] * (1.f / WSCALE)) * sc0 + sh0;
+                float v1 = (acc[m][1][r] * (1.f / WSCALE)) * sc1 + sh1;
+                if (relu) {
+                    v0 = fmaxf(v0, 0.f);
+                    v1 = fmaxf(v1, 0.f);
+                }
+                const size_t o = frame * (size_t)H * W * Cout + ((size_t)oy * W + ox) * Cout + co;
+                if (OUT_F32) {
+                    *reinterpret_cast<float2*>(out32 + o) = make_float2(v0, v1);
+                } else {
+                    const h2v v = {(half_t)v0, (half_t)v1};
+                    *reinterpret_cast<h2v*>(out16 + o) = v;
+                }
+            }
+        }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // first layer (3 -> 64 channels) on the split-fp16 MFMA as well.  The frame is first rewritten as two NHWC planes with
 // 4 channels per pixel (hi / lo halves, channel 3 = 0): 8 bytes per pixel and plane, so that the K index
 // k = tap * 4 + channel (25 taps -> K = 100, padded to 112 = 7 k-steps of 16) makes every 8-wide A fragment two
@@ -430,6 +564,136 @@ __global__ __launch_bounds__(256) void conv1_split_kernel(const h4v* __restrict_
             }
         }
     }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// first layer + BatchNorm + ReLU + blur-pool in one kernel (DTK_DD_FP16): the full-resolution 64-channel activation
+// (52 MB per 476 x 854 frame) is never written.  Same arithmetic as conv1_split_kernel<true> followed by
+// blurpool_half_kernel, value by value: the same K order (k = tap * 4 + channel, 7 MFMAs), the same BN fold, the
+// rounding to fp16 at the same place, and the 16 blur taps as one fp32 fmaf chain (i outer, j inner).
+//
+// A workgroup walks DOWN a band of C1F_OX = 30 pooled columns (64 conv columns: 2 ox0 - 2 .. 2 ox0 + 61, which covers
+// the reflected taps of both edges) for C1F_SEG pooled rows, with the 64 x 112 weights in registers all the way.  Per
+// step it computes one PAIR p of conv rows (2p - 1, 2p) x 64 columns -- wave w = row w >> 1, 32 columns -- into a ring
+// of three pairs in LDS and then blurs pooled row p - 1, which reads the pairs p - 2 .. p (rows 2o - 2 .. 2o + 2: the
+// taps 2o - 1 + i and, at the bottom of an odd-height map, the mirror image 2o - 2).  Rows and columns outside the
+// map are computed from reflected inputs and never read.  Vertical halo: two extra pairs per segment (5 % at 40 rows);
+// horizontal: 64 columns for 60 (7 %).
+// Weights: column j of N-tile n is output channel 2j + n, so that a lane holds the channel pair (2 li, 2 li + 1) of a
+// pixel and the epilogue is 16 ds_write_b32 of 128 contiguous bytes per pixel.  Even and odd conv columns live in
+// separate planes of the ring: the blur reads of a wave (8 pooled pixels x 8 pieces of 16 B) are then contiguous.
+// Resources (gfx950 code object), designed for three workgroups per CU = three waves per SIMD: 52 416 B LDS (ring 49 152
+// + input patch 3 264; 3 x 52 416 <= 160 KiB) and 146 VGPRs (<= 168 allows three waves per SIMD); no scratch, no spills.
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int C1F_OX = 30;               // pooled columns of a band
+constexpr int C1F_CW = 2 * C1F_OX + 4;   // conv columns of a band (64 = 2 waves x 32)
+constexpr int C1F_PW = C1F_CW + 4;       // input columns of the patch
+constexpr int C1F_SEG = 40;              // pooled rows of a workgroup
+static_assert(C1F_CW == 64, "a pair of conv rows is 4 waves x 32 pixels");
+
+__global__ __launch_bounds__(256) void conv1_pool_half_kernel(const h4v* __restrict__ in_hi, const half_t* __restrict__ Wh,
+                                                              const float* __restrict__ scale, const float* __restrict__ shift,
+                                                              half_t* __restrict__ out, int H, int W, int Ho, int Wo) {
+    __shared__ h4v Xp[6 * C1F_PW];                                                       // input rows 2p - 3 .. 2p + 2
+    __shared__ __attribute__((aligned(16))) half_t Ring[3 * 2 * 2 * (C1F_CW / 2) * 64];  // [pair % 3][row][column parity][32][64]
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int li = lane & 31, hh = lane >> 5;
+    const int ox0 = blockIdx.x * C1F_OX, oy0 = blockIdx.y * C1F_SEG;
+    const int oy1 = min(oy0 + C1F_SEG, Ho);
+    const int cx0 = 2 * ox0 - 2;
+    const size_t frame = blockIdx.z;
+    const h4v* fh = in_hi + frame * (size_t)H * W;
+    half_t* fout = out + frame * (size_t)Ho * Wo * 64;
+    // weights: B operand, lane (column li of tile n = channel 2 li + n, half hh) holds k = 16 ks + 8 hh .. + 7
+    h8 wh[2][C1_KS];
+    float sc[2], sh[2];
+#pragma unroll
+    for (int n = 0; n < 2; ++n) {
+#pragma unroll
+        for (int ks = 0; ks < C1_KS; ++ks)
+            wh[n][ks] = *reinterpret_cast<const h8*>(Wh + (size_t)(2 * li + n) * C1_K + ks * 16 + hh * 8);
+        sc[n] = scale[2 * li + n] * (1.f / WSCALE);
+        sh[n] = shift[2 * li + n];
+    }
+    const int sub = w >> 1, colbase = (w & 1) * 32;   // this wave's conv row of the pair and its 32 columns
+    // the input patch of the next pair travels through registers while this pair's MFMAs run (6 x 68 pixels of 8 bytes)
+    const int q0 = tid / C1F_PW, c0 = tid - q0 * C1F_PW;
+    const int q1 = (tid + 256) / C1F_PW, c1 = (tid + 256) - q1 * C1F_PW;
+    const bool second = tid + 256 < 6 * C1F_PW;
+    const int gx0 = reflect(cx0 - 2 + c0, W), gx1 = reflect(cx0 - 2 + c1, W);
+    h4v xr0, xr1 = {};
+#define C1F_FETCH(p_)                                                                   \
+    do {                                                                                \
+        xr0 = fh[(size_t)reflect(2 * (p_) - 3 + q0, H) * W + gx0];                      \
+        if (second) xr1 = fh[(size_t)reflect(2 * (p_) - 3 + q1, H) * W + gx1];          \
+    } while (0)
+    C1F_FETCH(oy0 - 1);
+    // blur: thread = (pooled pixel tid >> 3 of the band, 8 channels)
+    const int bpx = tid >> 3, bcq = tid & 7;
+    const int box = ox0 + bpx;
+    const bool blur_on = bpx < C1F_OX && box < Wo;
+    int bcol[4];   // ring offsets (halves) of the four columns of this thread's taps
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int c = reflect(2 * box - 1 + j, W) - cx0;   // 0 .. 63 for a live thread
+        bcol[j] = blur_on ? ((c & 1) * (C1F_CW / 2) + (c >> 1)) * 64 + bcq * 8 : 0;
+    }
+    for (int p = oy0 - 1; p <= oy1; ++p) {
+        Xp[tid] = xr0;
+        if (second) Xp[tid + 256] = xr1;
+        __syncthreads();
+        if (p < oy1) C1F_FETCH(p + 1);
+        f16v acc[2];
+#pragma unroll
+        for (int n = 0; n < 2; ++n)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[n][r] = 0.f;
+#pragma unroll
+        for (int ks = 0; ks < C1_KS; ++ks) {
+            // the 8 k values of this lane: taps t0 = 2 (2 ks + hh) and t0 + 1 (taps >= 25 carry zero weights: any valid pixel)
+            const int t0 = min(4 * ks + 2 * hh, 24), t1 = min(4 * ks + 2 * hh + 1, 24);
+            const h4v a0 = Xp[(sub + t0 / 5) * C1F_PW + colbase + li + t0 % 5];
+            const h4v a1 = Xp[(sub + t1 / 5) * C1F_PW + colbase + li + t1 % 5];
+            const h8 xh = {a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};
+#pragma unroll
+            for (int n = 0; n < 2; ++n) acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(xh, wh[n][ks], acc[n], 0, 0, 0);
+        }
+        // D[i][j]: j = li (channel pair), i = (r&3) + 8 (r>>2) + 4 hh (column of the wave's 32); BN fold + ReLU, fp16
+        half_t* rrow = Ring + (((p + 3) % 3) * 2 + sub) * (C1F_CW * 64);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int col = colbase + (r & 3) + 8 * (r >> 2) + 4 * hh;
+            const float v0 = fmaxf(acc[0][r] * sc[0] + sh[0], 0.f);
+            const float v1 = fmaxf(acc[1][r] * sc[1] + sh[1], 0.f);
+            const h2v v = {(half_t)v0, (half_t)v1};
+            *reinterpret_cast<h2v*>(rrow + ((col & 1) * (C1F_CW / 2) + (col >> 1)) * 64 + 2 * li) = v;
+        }
+        __syncthreads();
+        const int o = p - 1;
+        if (o >= oy0 && blur_on) {
+            const float f[4] = {1.f, 3.f, 3.f, 1.f};
+            float bacc[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) bacc[e] = 0.f;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int gy = reflect(2 * o - 1 + i, H);                      // conv row; pair (gy + 1) >> 1, row (gy + 1) & 1
+                const half_t* brow = Ring + ((((gy + 1) >> 1) % 3) * 2 + ((gy + 1) & 1)) * (C1F_CW * 64);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const float wgt = f[i] * f[j] * (1.f / 64.f);
+                    const h8 v = *reinterpret_cast<const h8*>(brow + bcol[j]);
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) bacc[e] = fmaf(wgt, (float)v[e], bacc[e]);
+                }
+            }
+            h8 ov;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) ov[e] = (half_t)bacc[e];
+            *reinterpret_cast<h8*>(fout + ((size_t)o * Wo + box) * 64 + bcq * 8) = ov;
+        }
+    }
+#undef C1F_FETCH
 }
 
 // NHWC blur-pool on split planes: one thread per (output pixel, 8 channels)
@@ -766,8 +1030,11 @@ extern "C" int dtk_delta_dino_refine(const dtk_geom* g, const float* video, cons
 extern "C" int dtk_delta_dino_refine_mode(const dtk_geom* g, const float* video, const float* dino,
                                           const float* const* packed, float* out, float* norms, int t0, int nframes,
                                           int operands, void* workspace, size_t workspace_bytes, void* stream) {
-    DTK_REQUIRE(operands == DTK_DD_SPLIT || operands == DTK_DD_FP16, "dtk_delta_dino_refine_mode: unknown operand mode");
-    const bool single = operands == DTK_DD_FP16;
+    DTK_REQUIRE(operands == DTK_DD_SPLIT || operands == DTK_DD_FP16 || operands == DTK_DD_FP16_V1,
+                "dtk_delta_dino_refine_mode: unknown operand mode");
+    const bool single = operands != DTK_DD_SPLIT;
+    // DTK_DD_FP16: conv1_pool_half_kernel and conv5x5_half_kernel; DTK_DD_FP16_V1: the kernels they replaced
+    const bool fused1 = operands == DTK_DD_FP16;
     DTK_REQUIRE(g && video && dino && packed && out && workspace, "dtk_delta_dino_refine: null pointer");
     DTK_REQUIRE(g->C % 4 == 0, "dtk_delta_dino_refine: C must be a multiple of 4");
     DTK_REQUIRE(t0 >= 0 && nframes >= 0 && t0 + nframes <= g->T, "dtk_delta_dino_refine: frame range out of bounds");
@@ -790,7 +1057,11 @@ extern "C" int dtk_delta_dino_refine_mode(const dtk_geom* g, const float* video,
                hipFuncSetAttribute(reinterpret_cast<const void*>(&conv5x5_split_kernel<1, true, true>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)SplitCfg<1>::LDS_BYTES_SINGLE) == hipSuccess &&
                hipFuncSetAttribute(reinterpret_cast<const void*>(&conv5x5_split_kernel<2, false, true>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)SplitCfg<2>::LDS_BYTES_SINGLE) == hipSuccess;
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)SplitCfg<2>::LDS_BYTES_SINGLE) == hipSuccess &&
+               hipFuncSetAttribute(reinterpret_cast<const void*>(&conv5x5_half_kernel<1, false>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)HalfCfg<1>::LDS_BYTES) == hipSuccess &&
+               hipFuncSetAttribute(reinterpret_cast<const void*>(&conv5x5_half_kernel<2, true>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)HalfCfg<2>::LDS_BYTES) == hipSuccess;
     }();
     DTK_REQUIRE(lds_ok, "dtk_delta_dino_refine: cannot reserve LDS for the split-fp16 convolution");
     for (int f0 = t0; f0 < t0 + nframes; f0 += fb) {
@@ -817,7 +1088,11 @@ extern "C" int dtk_delta_dino_refine_mode(const dtk_geom* g, const float* video,
                            npix);
                 const half_t* Wh = reinterpret_cast<const half_t*>(Wk + f32_packed_floats(cinp, coutp));
                 const int tiles_x = dtk_cdiv(W, C1_TX), tiles_y = dtk_cdiv(H, C1_TY);
-                if (half_path) {
+                if (half_path && fused1) {
+                    const int Ho = pool_out(H), Wo = pool_out(W);
+                    DTK_LAUNCH("dd_conv1", conv1_pool_half_kernel, dim3(dtk_cdiv(Wo, C1F_OX), dtk_cdiv(Ho, C1F_SEG), nf), dim3(256),
+                               0, st, vh, Wh, scale, shift, reinterpret_cast<half_t*>(ws + p.pool[l]), H, W, Ho, Wo);
+                } else if (half_path) {
                     DTK_LAUNCH("dd_conv1", conv1_split_kernel<true>, dim3(tiles_x * tiles_y, 1, nf), dim3(256), 0, st, vh, vl, Wh,
                                Wh + 64 * C1_K, scale, shift, (float*)nullptr, reinterpret_cast<half_t*>(act), H, W, tiles_x);
                 } else {
@@ -844,7 +1119,13 @@ extern "C" int dtk_delta_dino_refine_mode(const dtk_geom* g, const float* video,
                 half_t* oh = reinterpret_cast<half_t*>(act);
                 const int tiles_x = dtk_cdiv(W, STX), tiles_y = dtk_cdiv(H, STY);
                 dim3 grid(tiles_x * tiles_y, (cout + 63) / 64, nf);
-                if (l < 3 && single) {
+                if (l < 3 && fused1) {
+                    DTK_LAUNCH("dd_conv23", (conv5x5_half_kernel<1, false>), grid, dim3(256), HalfCfg<1>::LDS_BYTES, st, ih, Wh,
+                               scale, shift, oh, (float*)nullptr, H, W, cin, cout, 1, tiles_x);
+                } else if (fused1) {
+                    DTK_LAUNCH("dd_conv4", (conv5x5_half_kernel<2, true>), grid, dim3(256), HalfCfg<2>::LDS_BYTES, st, ih, Wh,
+                               scale, shift, (half_t*)nullptr, act, H, W, cin, cout, 0, tiles_x);
+                } else if (l < 3 && single) {
                     DTK_LAUNCH("dd_conv23", (conv5x5_split_kernel<1, true, true>), grid, dim3(256), SplitCfg<1>::LDS_BYTES_SINGLE,
                                st, ih, ih, Wh, Wl, scale, shift, oh, oh, (float*)nullptr, H, W, cin, cout, 1, tiles_x, 0, 0);
                 } else if (single) {
@@ -865,7 +1146,9 @@ extern "C" int dtk_delta_dino_refine_mode(const dtk_geom* g, const float* video,
                 const int Ho = pool_out(H), Wo = pool_out(W);
                 float* pl = ws + p.pool[l];
                 const size_t pool_n = (size_t)nf * Ho * Wo * cout;
-                if (!split) {
+                if (l == 0 && half_path && fused1) {
+                    // the pooled plane is already there (conv1_pool_half_kernel)
+                } else if (!split) {
                     const long long n = (long long)Ho * Wo * (cout / 4);
                     DTK_LAUNCH("dd_blurpool", blurpool_kernel, dim3(dtk_cdiv(n, 256), nf), dim3(256), 0, st, act, pl, H, W,
                                Ho, Wo, cout);

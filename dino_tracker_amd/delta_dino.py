@@ -43,13 +43,15 @@ def pack_weights(delta_dino, device):
 
 
 # Operand precision of the 5x5 convolutions of layers 2-4 (include/dtk.h: DTK_DD_SPLIT / DTK_DD_FP16).  A module attribute
-# `conv_operands` ("split" / "fp16") on the DeltaDINO instance wins over the environment variable DTK_P2_OPERANDS.
+# `conv_operands` ("split" / "fp16" / "fp16_v1") on the DeltaDINO instance wins over the environment variable DTK_P2_OPERANDS.
 # Default since round 4: plain fp16 operands (fp32 accumulation).  P1 already computes the DINO features with fp16 operands
 # (feature error 1.4e-4); the residual CNN's fp16 operands move the refined features by 1e-6 of that on top, and the
 # end-to-end error from the video stays where it was (p99 2.7e-4 px, max 3.7e-4 px, flags identical:
 # profiles/r04_e2e_error_p2_operands.json) for 20 ms less per 90-frame video.  "split" is the fp32-grade mode (3e-5 of the
 # reference's refined features) that the golden-file tests of P2 run.
-_OPERAND_MODES = {"split": 0, "fp16": 1}
+# "fp16_v1" (DTK_DD_FP16_V1): the values of "fp16", bit for bit, from the kernel sequence it ran before the first layer was fused
+# with its blur-pool -- the A / B switch (DTK_P2_OPERANDS=fp16_v1) and the reference of tests/test_gpu_p2_fp16_fused.py.
+_OPERAND_MODES = {"split": 0, "fp16": 1, "fp16_v1": 2}
 DEFAULT_CONV_OPERANDS = "fp16"
 
 

@@ -230,7 +230,13 @@ int dtk_delta_dino_refine(const dtk_geom* g, const float* video, const float* di
                           void* stream);
 /* The same with the operand precision of the 5x5 convolutions of layers 2-4 chosen by the caller:
  *   DTK_DD_SPLIT  every fp32 operand as hi + lo fp16 halves, three MFMA products per term (fp32-grade: 3e-5 of the reference)
- *   DTK_DD_FP16   the hi halves only: plain fp16 operands, fp32 accumulation, one product per term
+ *   DTK_DD_FP16   the hi halves only: plain fp16 operands, fp32 accumulation, one product per term.  The first layer, its
+ *                 BatchNorm + ReLU and the first blur-pool are ONE kernel (conv1_pool_half_kernel): the full-resolution
+ *                 64-channel activation is never written.  Layers 2-4 run on conv5x5_half_kernel (conflict-free LDS
+ *                 fragment reads, channel-pair stores: 4 bytes per lane in fp16, 8 in fp32).
+ *   DTK_DD_FP16_V1  the same values, bit for bit, from the kernel sequence DTK_DD_FP16 ran before those two kernels
+ *                 (conv1_split_kernel<true> + blurpool_half_kernel, conv5x5_split_kernel<.., SINGLE>): the A / B switch and the
+ *                 reference of tests/test_gpu_p2_fp16_fused.py.
  * DEFAULTS DIFFER BY ENTRY POINT, on purpose: dtk_delta_dino_refine (above, the round 1-3 entry) always means DTK_DD_SPLIT, so a
  * C caller that never heard of the mode keeps the fp32-grade result; the Python mirror (dino_tracker_amd/delta_dino.py) calls
  * THIS entry and defaults to DTK_DD_FP16 since round 4 (the end-to-end position error is unchanged to 1e-5 px behind the fp16
@@ -238,6 +244,7 @@ int dtk_delta_dino_refine(const dtk_geom* g, const float* video, const float* di
  * other).  tests/test_gpu_p2.py pins both modes against the reference-written golden, each with its own tolerance. */
 #define DTK_DD_SPLIT 0
 #define DTK_DD_FP16 1
+#define DTK_DD_FP16_V1 2
 int dtk_delta_dino_refine_mode(const dtk_geom* g, const float* video, const float* dino, const float* const* packed,
                                float* out, float* norms, int t0, int nframes, int operands, void* workspace,
                                size_t workspace_bytes, void* stream);

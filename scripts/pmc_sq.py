@@ -2,6 +2,9 @@
     SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU SQ_WAVES
 (MI355X_MICROARCH.md, PMC section: WAIT_ANY = wave parked on s_waitcnt / barrier, WAIT_INST_ANY = issue stall, ACTIVE_INST_ANY
 = issuing; the three are disjoint and sum to WAVE_CYCLES; SQ counters are in quad-cycles, MFMA_BUSY in cycles).
+A pass that carries SQ_LDS_BANK_CONFLICT and SQ_LDS_IDX_ACTIVE gets two more columns: the LDS array's active cycles as a share of
+the kernel's time (summed over the 256 CUs) and the share of those cycles that are bank-conflict replays.  SQ_WAVE_CYCLES must be in
+every pass (rows are ordered by it and rows without it are dropped); a column whose counter the pass did not collect prints "–".
 
 Usage: python scripts/pmc_sq.py <pmc.db> > profiles/<round>_pmc_sq.md"""
 import re
@@ -56,16 +59,24 @@ for kn, cn, n, v in rows:
         seen.add(kn)
         t["ns"] += dur.get(kn, 0)
         t["launches"] += n
-print("| kernel | launches | ms (this pass) | parked % | issue-stall % | issuing % | VALU issue % | VALU instr / wave | MFMA pipe busy % of kernel time |")
-print("|---|---:|---:|---:|---:|---:|---:|---:|---:|")
+has_lds = any("SQ_LDS_IDX_ACTIVE" in t for t in tab.values())
+print("| kernel | launches | ms (this pass) | parked % | issue-stall % | issuing % | VALU issue % | VALU instr / wave | MFMA pipe busy % of kernel time |"
+      + (" LDS active % of kernel time | bank-conflict % of LDS active |" if has_lds else ""))
+print("|---|---:|---:|---:|---:|---:|---:|---:|---:|" + ("---:|---:|" if has_lds else ""))
 for k, t in sorted(tab.items(), key=lambda kv: -kv[1].get("SQ_WAVE_CYCLES", 0))[:24]:
     wc = t.get("SQ_WAVE_CYCLES", 0.0)
     if wc <= 0:
         continue
-    pct = lambda c: 100.0 * t.get(c, 0.0) / wc
+    pct = lambda c: f"{100.0 * t[c] / wc:.1f}" if c in t else "–"
     waves = max(t.get("SQ_WAVES", 0.0), 1.0)
     # MFMA_BUSY is summed over the 1024 SIMDs of the chip; kernel time in cycles at ~2.1 GHz
-    busy = 100.0 * t.get("SQ_VALU_MFMA_BUSY_CYCLES", 0.0) / (1024.0 * t["ns"] * 2.1) if t["ns"] else 0.0
-    print(f"| {k} | {t['launches']} | {t['ns'] / 1e6:.2f} | {pct('SQ_WAIT_ANY'):.1f} | {pct('SQ_WAIT_INST_ANY'):.1f} | "
-          f"{pct('SQ_ACTIVE_INST_ANY'):.1f} | {pct('SQ_ACTIVE_INST_VALU'):.1f} | {t.get('SQ_INSTS_VALU', 0.0) / waves:.0f} | {busy:.1f} |")
+    busy = f"{100.0 * t['SQ_VALU_MFMA_BUSY_CYCLES'] / (1024.0 * t['ns'] * 2.1):.1f}" if t["ns"] and "SQ_VALU_MFMA_BUSY_CYCLES" in t else "–"
+    per_wave = f"{t['SQ_INSTS_VALU'] / waves:.0f}" if "SQ_INSTS_VALU" in t else "–"
+    lds = ""
+    if has_lds:
+        act = t.get("SQ_LDS_IDX_ACTIVE", 0.0)
+        lds = (f" {100.0 * act / (256.0 * t['ns'] * 2.1) if t['ns'] else 0.0:.1f} | "
+               f"{100.0 * t.get('SQ_LDS_BANK_CONFLICT', 0.0) / act if act else 0.0:.1f} |")
+    print(f"| {k} | {t['launches']} | {t['ns'] / 1e6:.2f} | {pct('SQ_WAIT_ANY')} | {pct('SQ_WAIT_INST_ANY')} | "
+          f"{pct('SQ_ACTIVE_INST_ANY')} | {pct('SQ_ACTIVE_INST_VALU')} | {per_wave} | {busy} |" + lds)
 print("\n(percentages of SQ_WAVE_CYCLES; `MFMA pipe busy` assumes 1024 SIMDs and 2.1 GHz under load: an estimate)")
