@@ -48,9 +48,8 @@ class VitModel(ctypes.Structure):
                 ("tap_out", c_void_p), ("tap_mask", ctypes.c_uint64), ("tap_scale", ctypes.c_float)]
 
 
-VIT_TILED_GEMMS, VIT_BF16, VIT_CHECK_RANGE, VIT_ATTENTION_V2, VIT_GEMM_WS_V1, VIT_ATTENTION_V4, VIT_GEMM_WIDE_V1, VIT_NO_LN_FUSION = 1, 2, 4, 8, 16, 32, 64, 128  # dtk_vit_model.flags
-OPERAND_F16, OPERAND_BF16, OPERAND_ATTENTION_V2, OPERAND_ATTENTION_V4 = 0, 1, 0x100, 0x2000
-OPERAND_ATTENTION_V5, OPERAND_ATTENTION_V5_INPHASE = 0x200, 0x400   # stand-alone stage only: the round-5 experiment kernel (vit_attention5.h)
+VIT_TILED_GEMMS, VIT_BF16, VIT_CHECK_RANGE, VIT_GEMM_WS_V1, VIT_ATTENTION_V4, VIT_GEMM_WIDE_V1, VIT_NO_LN_FUSION = 1, 2, 4, 16, 32, 64, 128  # dtk_vit_model.flags (8 is retired)
+OPERAND_F16, OPERAND_BF16, OPERAND_ATTENTION_V4 = 0, 1, 0x2000
 VIT_GEMM_QKV, VIT_GEMM_QKV_FACET, VIT_GEMM_PROJ, VIT_GEMM_FC1, VIT_GEMM_FC2 = 0, 1, 2, 3, 4   # dtk_vit_gemm_args.role
 
 

@@ -14,17 +14,17 @@
 //                       so that every per-query quantity is lane-local; K / V^T tiles by LDS-DMA into XOR-swizzled images;
 //                       ONE wave per SIMD with 64 queries, its two query tiles half a key tile out of phase (the softmax of
 //                       one runs under the MFMAs of the other), fragments held in registers for both; exp2-domain softmax
-//                       with optimistic exponentials (guarded); XCD-aware grid.  attention2_kernel (vit_attention2.h: 16
-//                       waves per CU, 32 queries each; rounds 2-3) stays selectable (DTK_VIT_ATTENTION_V2) as the cross-check.
+//                       with optimistic exponentials (guarded); XCD-aware grid.  The one fallback / cross-check
+//                       (DTK_VIT_ATTENTION_V4) since round 6.
+//   attention6_kernel   (vit_attention6.h; round 6) the same arithmetic, tile layout and guards with 128 queries per wave: what
+//                       dtk_vit_forward runs.  (The round 2-3 kernel lives on in scripts/ubench/ for the micro-benchmark only.)
 // Residual stream fp32.  Matrix operands (LN output, Q / K / V^T / P, attention output, MLP hidden, the pending residual
 // update, the weights) are a template parameter T: _Float16 by default since round 3 -- the same MFMA rate as bf16 with
 // 8x less operand rounding (fp16 range: activations saturate at +-65504, FP16_OVFL mode, and set the model's overflow
 // word) -- or __bf16 with DTK_VIT_BF16 (the reference runs fp32; parity is stated in DESIGN.md section 4).
 #include <stdlib.h>
 #include "common.h"
-#include "vit_attention2.h"
 #include "vit_attention4.h"
-#include "vit_attention5.h"
 #include "vit_attention6.h"
 #include "vit_gemm_common.h"
 #include "vit_gemm_tiled.h"
@@ -377,32 +377,12 @@ VitPlan vit_plan(const dtk_vit_model* m, int ph, int pw, int frames) {
     return p;
 }
 
-// attention launch (vit_run, dtk_vit_attention).  variant 2: attention2 (DTK_VIT_ATTENTION_V2 / DTK_OPERAND_ATTENTION_V2);
-// 4: attention4 (rounds 4-5: 64 queries per wave; DTK_VIT_ATTENTION_V4 / DTK_OPERAND_ATTENTION_V4); >= 5: attention5 (round-5
-// experiment, stand-alone stage only: two waves per SIMD; fp16: variant = 5 + its ablation bits, bf16: the full form whatever the
-// bits); anything else: attention6.
+// attention launch (vit_run, dtk_vit_attention): attention6, or with v4 (DTK_VIT_ATTENTION_V4 / DTK_OPERAND_ATTENTION_V4) attention4
+// (rounds 4-5: 64 queries per wave), the fallback / cross-check.
 template <typename T>
-int attention_launch(const T* q, const T* k, const T* vt, T* o, int S, int Sp, int heads, int D, int FH, int variant,
-                     hipStream_t st) {
+int attention_launch(const T* q, const T* k, const T* vt, T* o, int S, int Sp, int heads, int D, int FH, bool v4, hipStream_t st) {
     int QB;
-    if (variant == 2) {
-        const unsigned grid = attn::attention_grid(FH, S, 256, &QB);
-        DTK_LAUNCH("vit_attention", (attn::attention2_kernel<T, 1>), dim3(grid), dim3(512), 0, st, q, k, vt, o, S, Sp, heads, D,
-                   FH, QB);
-    } else if (variant >= 5) {
-        const unsigned grid = attn::attention_grid(FH, S, 512, &QB);
-        if constexpr (IsF16<T>::value) {
-#define DTK_A5(V, ABLV)                                                                                                   \
-    if (variant == V)                                                                                                     \
-        DTK_LAUNCH("vit_attention", (attn::attention5_kernel<T, ABLV>), dim3(grid), dim3(512), 0, st, q, k, vt, o, S, Sp, heads, \
-                   D, FH, QB);
-            DTK_A5(5, 0) DTK_A5(6, 32) DTK_A5(7, 8 | 64) DTK_A5(8, 8 | 32 | 64) DTK_A5(9, 8 | 128) DTK_A5(10, 8 | 32 | 128)
-#undef DTK_A5
-        } else {
-            DTK_LAUNCH("vit_attention", (attn::attention5_kernel<T, 0>), dim3(grid), dim3(512), 0, st, q, k, vt, o, S, Sp, heads,
-                       D, FH, QB);
-        }
-    } else if (variant == 4) {
+    if (v4) {
         const unsigned grid = attn::attention_grid(FH, S, 256, &QB);
         DTK_LAUNCH("vit_attention", (attn::attention4_kernel<T, 0>), dim3(grid), dim3(256), 0, st, q, k, vt, o, S, Sp, heads, D,
                    FH, QB);
@@ -642,7 +622,7 @@ int vit_run(const dtk_vit_model* m, const float* frames, int nframes, int video_
             e.qscale = 0.125f * 1.4426950408889634f; e.no_store = dbg_ns; e.ovf = epi_ovf;
             if (launch_gemm<T, EPI_QKV>("vit_gemm_qkv", path, xn, qkv_w, rows, 3 * D, D, e, st)) return DTK_E_HIP;
             if (scan_all && scan_range(q, (long long)(p.ao - p.q) / 2, 2)) return DTK_E_HIP;
-            if (attention_launch(q, k, vt, ao, S, Sp, m->heads, D, nf * m->heads, (m->flags & DTK_VIT_ATTENTION_V2) ? 2 : ((m->flags & DTK_VIT_ATTENTION_V4) ? 4 : 0), st)) return DTK_E_HIP;
+            if (attention_launch(q, k, vt, ao, S, Sp, m->heads, D, nf * m->heads, (m->flags & DTK_VIT_ATTENTION_V4) != 0, st)) return DTK_E_HIP;
             e = GemmEpi<T>{};
             e.bias = L.proj_b; e.delta = delta; e.gamma = L.ls1; e.no_store = dbg_ns;
             if (launch_gemm<T, EPI_DELTA>("vit_gemm_proj", path, ao, proj_w, rows, D, D, e, st)) return DTK_E_HIP;
@@ -781,6 +761,10 @@ int vit_gemm_split_stage(const dtk_vit_gemm_args* g, int N, int K, hipStream_t s
     }
 }
 
+// every DTK_VIT_* bit of dtk_vit_model.flags that include/dtk.h defines (bit 8 is retired and not reused)
+constexpr int VIT_KNOWN_FLAGS = DTK_VIT_TILED_GEMMS | DTK_VIT_BF16 | DTK_VIT_CHECK_RANGE | DTK_VIT_GEMM_WS_V1 | DTK_VIT_ATTENTION_V4 |
+                                DTK_VIT_GEMM_WIDE_V1 | DTK_VIT_NO_LN_FUSION;
+
 }  // namespace
 
 extern "C" size_t dtk_vit_workspace_bytes(const dtk_vit_model* m, int video_h, int video_w, int frames) {
@@ -793,6 +777,8 @@ extern "C" int dtk_vit_forward(const dtk_vit_model* m, const float* frames, int 
                                float* tokens_out, float* feat_out, float* qkv_out, void* workspace,
                                size_t workspace_bytes, void* stream) {
     DTK_REQUIRE(m && frames && workspace && (tokens_out || feat_out || qkv_out || m->tap_out), "dtk_vit_forward: null pointer");
+    DTK_REQUIRE(!(m->flags & ~VIT_KNOWN_FLAGS), "dtk_vit_forward: unknown flag bits 0x%x (bit 8 selected a kernel that left the library)",
+                (unsigned)(m->flags & ~VIT_KNOWN_FLAGS));
     DTK_REQUIRE(!qkv_out || m->depth > 0, "dtk_vit_forward: qkv_out needs at least one block");
     DTK_REQUIRE(m->D > 0 && m->heads > 0 && m->D == m->heads * 64, "dtk_vit_forward: d_head must be 64 (D=%d heads=%d)",
                 m->D, m->heads);
@@ -817,21 +803,16 @@ extern "C" int dtk_vit_attention(const void* q, const void* k, const void* vt, v
                                  int Sp, int operand_type, void* stream) {
     DTK_REQUIRE(q && k && vt && out, "dtk_vit_attention: null pointer");
     DTK_REQUIRE(frames > 0 && heads > 0 && S > 0 && Sp >= S && Sp % 64 == 0, "dtk_vit_attention: bad sizes (Sp %% 64 == 0, Sp >= S)");
-    int variant = (operand_type & DTK_OPERAND_ATTENTION_V2) ? 2 : ((operand_type & DTK_OPERAND_ATTENTION_V4) ? 4 : 0);
-    if (operand_type & DTK_OPERAND_ATTENTION_V5) {   // 5 full, 6 in phase; micro-benchmark ablations (results are garbage): 7 / 8 no vector work, 9 / 10 no matrix work
-        const int inph = (operand_type & DTK_OPERAND_ATTENTION_V5_INPHASE) ? 1 : 0;
-        variant = 5 + inph + ((operand_type & 0x800) ? 2 : 0) + ((operand_type & 0x1000) ? 4 : 0);
-        DTK_REQUIRE(variant <= 10, "dtk_vit_attention: ablation bits 0x800 and 0x1000 exclude each other");
-    }
-    operand_type &= ~(DTK_OPERAND_ATTENTION_V2 | DTK_OPERAND_ATTENTION_V4 | DTK_OPERAND_ATTENTION_V5 | DTK_OPERAND_ATTENTION_V5_INPHASE | 0x800 | 0x1000);
+    const bool v4 = (operand_type & DTK_OPERAND_ATTENTION_V4) != 0;
+    operand_type &= ~DTK_OPERAND_ATTENTION_V4;   // any other bit (the retired kernel selections among them) is refused below
     DTK_REQUIRE(operand_type == DTK_OPERAND_F16 || operand_type == DTK_OPERAND_BF16, "dtk_vit_attention: operand_type");
     if (operand_type == DTK_OPERAND_BF16)
         return attention_launch(reinterpret_cast<const __bf16*>(q), reinterpret_cast<const __bf16*>(k),
                                 reinterpret_cast<const __bf16*>(vt), reinterpret_cast<__bf16*>(out), S, Sp, heads, heads * 64,
-                                frames * heads, variant, dtk_stream(stream));
+                                frames * heads, v4, dtk_stream(stream));
     return attention_launch(reinterpret_cast<const _Float16*>(q), reinterpret_cast<const _Float16*>(k),
                             reinterpret_cast<const _Float16*>(vt), reinterpret_cast<_Float16*>(out), S, Sp, heads, heads * 64,
-                            frames * heads, variant, dtk_stream(stream));
+                            frames * heads, v4, dtk_stream(stream));
 }
 
 // The same stage on split operands (vit_split.h: the escalated precision): hi / lo planes of every operand and of the output.

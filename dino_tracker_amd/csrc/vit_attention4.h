@@ -1,11 +1,11 @@
 // vit_attention4.h -- flash attention for d_head = 64, third generation (round 4): ONE wave per SIMD, 64 queries per wave.
 //
-// It keeps attention2's tile layout (K tile + V^T tile of 64 keys, 16-byte pieces XOR-swizzled through the DMA's source address),
-// its fp16 range guards (MODE 1 of attention2_kernel: estimated reference, RESC_T / POISON_T, safe pass) and its output layout.
-// What changes is the shape of the work inside a CU.
+// It keeps the tile layout of the round 2-3 kernel, attention2 (K tile + V^T tile of 64 keys, 16-byte pieces XOR-swizzled through the
+// DMA's source address), its fp16 range guards (vit_attention_common.h, "the guard arithmetic": estimated reference, RESC_T /
+// POISON_T, safe pass) and its output layout.  What changes is the shape of the work inside a CU.
 //
-// Why: attention2's wave owns 32 queries, so every 32x32x16 MFMA needs its own 1 KB
-// A fragment from LDS -- at the full MFMA rate that is 128 B per clock per CU, the LDS peak -- and its 16 waves per CU run
+// Why: attention2's wave owned 32 queries, so every 32x32x16 MFMA needs its own 1 KB
+// A fragment from LDS -- at the full MFMA rate that is 128 B per clock per CU, the LDS peak -- and its 16 waves per CU ran
 // QK^T -> softmax -> PV in sequence behind one barrier per tile: its ablation with NO softmax and NO DMA tops out at 1.30 PF.
 // Here a workgroup is 4 waves, one per SIMD, with the whole register file (launch bound 256 threads, 1 wave per SIMD),
 // and a wave owns TWO 32-query tiles:
@@ -20,7 +20,7 @@
 //        E(t):  MFMA  S(1,t) [K(t)], PV(1,t-1) [V(t-1)]    VALU  softmax(0,t)     LDS: kf <- K(t+1), vf <- V(t) after last use
 //        O(t):  MFMA  PV(0,t) [V(t)], S(0,t+1) [K(t+1)]    VALU  softmax(1,t)
 //   * K / V^T tiles by LDS-DMA into a ring of four 16 KB buffers, requested three tiles ahead, one barrier per key tile.
-// Arithmetic is attention2's MODE 1 (optimistic exponentials against an estimated reference, guarded).
+// Arithmetic: the guard arithmetic of vit_attention_common.h (optimistic exponentials against an estimated reference, guarded).
 #pragma once
 #include "vit_attention_common.h"
 
@@ -134,7 +134,7 @@ __global__ __launch_bounds__(256, 1) void attention4_kernel(const T* __restrict_
     op8 kf[8], vf[8];
     // The reference of a query enters its scores through the C operand of the first MFMA of every score block: every
     // accumulator register of a lane belongs to ONE query (the column), so C = (-m, ..., -m) makes the matrix pipe deliver
-    // s - m at no VALU cost (attention2 needed a subtracting and a non-subtracting copy of its loop for this).
+    // s - m at no VALU cost (the round 2-3 kernel needed a subtracting and a non-subtracting copy of its loop for this).
     float m_run[2] = {0.f, 0.f};
     f16v negm[2];
     float l_run[2] = {0.f, 0.f};
@@ -165,7 +165,7 @@ __global__ __launch_bounds__(256, 1) void attention4_kernel(const T* __restrict_
     for (int qt = 0; qt < 2; ++qt)
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) asm volatile("" ::"v"(qf[qt][ks]));
-    // reference estimate (attention2 MODE 1): keys 0..63 and the query tile's own 32 keys
+    // reference estimate (vit_attention_common.h): keys 0..63 and the query tile's own 32 keys
     if (!(ABL & 8)) {
 #pragma unroll
         for (int qt = 0; qt < 2; ++qt) {
@@ -216,7 +216,7 @@ __global__ __launch_bounds__(256, 1) void attention4_kernel(const T* __restrict_
                 if (key >= S) s2[b][r] = -1e30f;
             }
     };
-    // rare: a lane's 32-key part of the tile's row sum of query tile qt passed RESC_T (attention2 MODE 1, same arithmetic);
+    // rare: a lane's 32-key part of the tile's row sum of query tile qt passed RESC_T (vit_attention_common.h, the guard arithmetic);
     // called after the PV product of that tile has been issued.  The scores of the NEXT key tile are already in sc[qt]
     // (computed against the old reference): they move with it.
     auto guard_tripped = [&](int qt, float lsum) {

@@ -25,7 +25,7 @@
 //            bookkeeping: counted waits (lgkmcnt(8) in front of the barrier, lgkmcnt(0) in slot 7 of sub-step 0)
 //     DMA    sub-step 0, slots 2, 6, 10, 14: the four requests of tile t + 3 (ring of four buffers, as attention4)
 // Score sets alternate between two register sets with every sub-step (four tiles: tile u uses set u & 1).
-// Arithmetic is attention4's (attention2 MODE 1): optimistic exponentials against a reference estimated once per query, a guard on
+// Arithmetic is attention4's (vit_attention_common.h, "the guard arithmetic"): optimistic exponentials against a reference estimated once per query, a guard on
 // every tile's row sum, the rescale AFTER the PV product of the tile that tripped it (here: after sub-step u of the next key tile, where
 // PV(u, t) and S(u, t + 1) are issued -- the scores of key tile t + 1 move with the reference), poison and the safe pass.
 #pragma once
@@ -139,7 +139,7 @@ __global__ __launch_bounds__(256, 1) void attention6_kernel(const T* __restrict_
         for (int ks = 0; ks < 4; ++ks) asm volatile("" : "+a"(qf[qt][ks]));
     __syncthreads();   // tiles 0 .. 2 of every wave have landed
 
-    // reference estimate (attention2 MODE 1): keys 0..63 and the query tile's own 32 keys, while the first tiles are in flight
+    // reference estimate (vit_attention_common.h): keys 0..63 and the query tile's own 32 keys, while the first tiles are in flight
     float m_run[NQ], l_run[NQ];
 #pragma unroll
     for (int qt = 0; qt < NQ; ++qt) { m_run[qt] = 0.f; l_run[qt] = 0.f; }
@@ -229,7 +229,7 @@ __global__ __launch_bounds__(256, 1) void attention6_kernel(const T* __restrict_
                 if (key >= S) s2[b][r] = -1e30f;
             }
     };
-    // rare: a lane's 32-key part of a tile's row sum of query tile qt passed RESC_T (attention2 MODE 1, same arithmetic); called after
+    // rare: a lane's 32-key part of a tile's row sum of query tile qt passed RESC_T (vit_attention_common.h, the guard arithmetic); called after
     // the PV product of that key tile has been issued.  The scores of the NEXT key tile, computed against the old reference, are in
     // score set `set`: they move with it.
     auto guard_tripped = [&](auto qt_tag, auto set_tag, float lsum, bool scores_live) {

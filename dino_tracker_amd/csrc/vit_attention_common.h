@@ -1,9 +1,29 @@
-// vit_attention_common.h -- what the flash-attention kernels for d_head = 64 (vit_attention2 / 4 / 5 / 6.h) share: the operand
-// type, the K / V^T tile layout, the fp16 range guards, the safe pass, the grid and the AGPR helpers.
+// vit_attention_common.h -- what the flash-attention kernels for d_head = 64 (vit_attention4.h, vit_attention6.h) share: the
+// operand type, the K / V^T tile layout, the fp16 range guards, the safe pass, the grid and the AGPR helpers.
 //
 // fp16 is the default operand type of the library since round 3: the same MFMA rate as bf16 with 8x less operand rounding (round
 // 2's end-to-end error from the VIDEO, p99 1.4e-3 px, was the bf16 operands of P1).  fp16's narrow exponent range is what the
-// guards of attention2's MODE 1 (and of the later kernels, which use its arithmetic) are sized for.
+// guards below are sized for.
+//
+// THE GUARD ARITHMETIC (optimistic exponentials; both kernels use it unchanged since round 2).  With d_head = 64 the softmax
+// costs as many VALU cycles as the tile costs MFMA cycles, and a third of them only maintain the running maximum.  Any reference
+// m gives the same softmax as long as 2^(s - m) stays inside the range in which P keeps its precision: bf16 has fp32's exponent
+// range; fp16 ends at 65504 above and has full precision down to 2^-14 only.
+//   * The reference is ESTIMATED ONCE per query, before the key loop: the maximum of its scores against the first 64 keys (which
+//     hold the CLS token) and against the 32 keys of its own query tile (which hold its own key: the self score is the usual row
+//     maximum of a trained ViT).  That is a lower bound of the row maximum, hence p_max >= 1.  The kernels feed -m to the scores
+//     through the C operand of the first MFMA of a score block, so subtracting it costs no VALU work.
+//   * In the loop only a guard on the tile's row sum runs, one compare per tile: not (a lane's 32-key part < Operand::RESC_T),
+//     which also catches inf / NaN.  Nothing has overflowed yet while the part stays below Operand::POISON_T (fp16: RESC_T = 2^9,
+//     POISON_T = 2^15, so every p < 65504; bf16: 2^40 / 2^120).
+//   * The power-of-two rescale: after the tile's PV product the wave moves the reference up by k = floor(log2(tile sum)), i.e.
+//     scales l and O by the exact power of two 2^-k (scores already computed against the old reference move by -k with it).
+//     The reference therefore never exceeds the row maximum by more than 6 binades (k <= log2(64 p_max)), so p_max >= 2^-6 and
+//     the entries that matter at 11 bits are normal numbers.
+//   * A part beyond POISON_T in ONE step (fp16: a score 15 binades = 10 nats above everything the row has seen; bf16: 120
+//     binades) poisons the row sum (NaN) instead.  A wave that finds a poisoned or a tiny (< Operand::LOW_T) sum at the end
+//     redoes its queries in safe_pass below: running maximum per tile, operands straight from global memory, no barriers.
+// tests/test_gpu_p1.py::test_attention_guards_and_safe_pass forces all of these events on both kernels.
 #pragma once
 #include <type_traits>
 #include "common.h"
@@ -24,8 +44,8 @@ struct Operand {
         if constexpr (F16) return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
         else return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
     }
-    // MODE 1 thresholds on a lane's part (32 keys) of a tile's row sum: at RESC_T the reference moves up after the tile; at
-    // POISON_T a P entry may have left the operand type's range (fp16: 65504), the row is redone by the safe pass
+    // guard thresholds (file comment) on a lane's part (32 keys) of a tile's row sum: at RESC_T the reference moves up after the tile;
+    // at POISON_T a P entry may have left the operand type's range (fp16: 65504), the row is redone by the safe pass
     static constexpr float RESC_T = F16 ? 0x1p9f : 0x1p40f;
     static constexpr float POISON_T = F16 ? 0x1p15f : 0x1p120f;
     static constexpr float LOW_T = F16 ? 0x1p-7f : 0x1p-100f;  // a final row sum below this has lost P's precision (fp16 subnormals)
@@ -33,7 +53,7 @@ struct Operand {
 
 constexpr int TILE_KEYS = 64;
 constexpr int TILE_BYTES = 2 * TILE_KEYS * 64 * 2;  // K tile (64 keys x 64 d) + V^T tile (64 d x 64 keys), bf16
-constexpr int A4_NB = 4;        // LDS ring of attention4 / 5 / 6 (buffers of TILE_BYTES)
+constexpr int A4_NB = 4;        // LDS ring of attention4 / 6 (buffers of TILE_BYTES)
 constexpr int A4_AHEAD = 3;     // tiles requested ahead of the one whose V^T part is being read
 
 // 1-D grid of 8 * ceil(FH / 8) * QB workgroups, QB = ceil(S / queries per workgroup).  Workgroup b runs on XCD b % 8; a kernel maps
@@ -56,14 +76,16 @@ __device__ __forceinline__ void halves(float x, float& lo_all, float& hi_all) {
     hi_all = __uint_as_float(r1);  // the value held by the upper-half lane
 }
 
-// Safe pass of ONE wave (rare: only after a poisoned row sum, MODE 1): queries q0 .. q0+nq-1 of one (frame, head) again,
+// Safe pass of ONE wave (rare: only after a poisoned or tiny row sum): queries q0 .. q0+nq-1 of one (frame, head) again,
 // 32 at a time, with a running maximum per 64-key tile; fragments come straight from global memory in the layouts of the
 // main loop (K rows permuted so that a lane holds 8 consecutive keys per 16-key group), no LDS, no barriers.
 // TAG: one instantiation per kernel family -- an out-of-line device function is compiled ONCE per instantiation with the
 // register budget of its most generous caller, and every caller then inherits that allocation (round 3: next to a
 // 256-register kernel the shared safe pass cost the 128-register kernel half its occupancy).
-// (safe_pass_impl: the body, inlined where the caller wants the pass inside its OWN register budget -- attention5 runs two waves
-//  per SIMD and an out-of-line callee is compiled to the caller's VGPR budget without knowing about its AGPRs)
+// (safe_pass_impl: the body.  Its only caller is safe_pass, but writing it straight into the __noinline__ function is not a neutral
+//  edit: hipcc then compiles the pass differently (fp16: 690 instead of 623 instructions) and, since a caller's register allocation
+//  knows what its callee clobbers, attention4_kernel and attention6_kernel change with it (scripts/isa_diff.py).  Fold it only
+//  together with a measurement of both kernels.)
 template <typename T>
 __device__ __forceinline__ void safe_pass_impl(const T* Qb, const T* Kb, const T* Vb, T* Ob, int q0, int nq, int S, int Sp,
                                                int D) {

@@ -126,8 +126,7 @@ typedef struct dtk_vit_model {
 #define DTK_VIT_TILED_GEMMS 1   /* run the K = 384 GEMMs on the tiled kernel too (cross-check in the tests) */
 #define DTK_VIT_BF16 2          /* operand type bf16 instead of fp16 (weights must then be bf16) */
 #define DTK_VIT_CHECK_RANGE 4   /* scan Q / K / V^T and the MLP hidden of every block for saturated values (costs a pass) */
-#define DTK_VIT_ATTENTION_V2 8  /* attention on the round-2/3 kernel (16 waves per CU x 32 queries) instead of the one-wave-per-SIMD
-                                 * kernel of round 4: the cross-check path of the tests */
+/* (8 selected the round-2/3 attention kernel until it left the library: retired, not reused; dtk_vit_forward refuses unknown bits) */
 #define DTK_VIT_GEMM_WS_V1 16   /* the K = 384 weight-stationary GEMMs in their round 1-3 form (A / B measurement, cross-check) */
 #define DTK_VIT_ATTENTION_V4 32 /* attention on the round-4/5 kernel (one wave per SIMD, 64 queries per wave: csrc/vit_attention4.h) instead of
                                  * round 6's 128 queries per wave (csrc/vit_attention6.h): A / B measurement, cross-check */
@@ -138,13 +137,8 @@ typedef struct dtk_vit_model {
                                  * at the top of every k-step (A / B measurement, cross-check: the results are bit-identical) */
 #define DTK_OPERAND_F16 0
 #define DTK_OPERAND_BF16 1
-#define DTK_OPERAND_ATTENTION_V2 0x100  /* OR-ed into dtk_vit_attention's operand_type: the same selection for the stand-alone stage */
-#define DTK_OPERAND_ATTENTION_V4 0x2000 /* the same selection as DTK_VIT_ATTENTION_V4 for the stand-alone stage */
-#define DTK_OPERAND_ATTENTION_V5 0x200  /* stand-alone stage only: the round-5 EXPERIMENT kernel, two waves per SIMD alternating matrix /
-                                         * vector phases (csrc/vit_attention5.h); measured against the library's kernel by
-                                         * scripts/attn_ab.py, not used by dtk_vit_forward */
-#define DTK_OPERAND_ATTENTION_V5_INPHASE 0x400  /* with ..._V5: both wave halves in phase (the experiment's ablation); 0x800 / 0x1000 with
-                                                 * ..._V5: micro-benchmark ablations WITHOUT meaningful output (no vector / no matrix work) */
+#define DTK_OPERAND_ATTENTION_V4 0x2000 /* OR-ed into dtk_vit_attention's operand_type: the same selection as DTK_VIT_ATTENTION_V4 for the
+                                         * stand-alone stage; every other bit is refused */
 
 /* frames [n][3][video_h][video_w] fp32 in [0,1] -> block output of layer depth-1 (before the final norm):
  * tokens_out [n][1 + ph*pw][D] (CLS first; what get_feature_from_input returns) and/or

@@ -1,6 +1,6 @@
 """Same-box A / B of the stand-alone attention stage between two builds of libdtk.so (ctypes handles of both in one process):
-    python scripts/attn_ab.py <lib A>[:flags] <lib B>[:flags] [<lib C>[:flags] ...]      (flags: OR-ed into operand_type, e.g. 0x200 =
-    DTK_OPERAND_ATTENTION_V5, 0x600 = the same with both wave halves in phase, 0x100 = attention2)
+    python scripts/attn_ab.py <lib A>[:flags] <lib B>[:flags] [<lib C>[:flags] ...]      (flags: OR-ed into operand_type: 0x2000 =
+    DTK_OPERAND_ATTENTION_V4, the attention4 kernel; none = attention6.  A current library refuses every other bit.)
 Benchmark shapes (frames x 6 heads, S = 8108, random fp16 operands), alternating blocks of launches, hipEvents around each block."""
 import ctypes
 import sys

@@ -6,8 +6,8 @@
 Unbundles the gfx950 code object (the objcopy + clang-offload-bundler recipe of tests/test_abi.py::test_m0_users and
 scripts/kernel_resources.sh), disassembles it and compares, per function symbol, the instruction list -- addresses and
 encodings dropped; s_call targets and the pc-relative literal behind an s_getpc_b64 (s_add_u32 / s_addc_u32 sN, sN, 0x...)
-replaced by a placeholder, because they move when ANOTHER function changes size; branches inside a function are pc-relative
-and stay as they are -- and, per kernel, the register, spill, LDS and scratch figures of the metadata notes.  Prints the
+replaced by a placeholder, and the s_nop 0 padding behind a function's last instruction dropped, because they move when ANOTHER
+function changes size; branches inside a function are pc-relative and stay as they are -- and, per kernel, the register, spill, LDS and scratch figures of the metadata notes.  Prints the
 functions that differ; exit status 1 if any do."""
 import os
 import re
@@ -53,6 +53,9 @@ def functions(co):
             ins = f"{m.group(1)} {m.group(2)}, {m.group(3)}, <pcrel>"
         ins = re.sub(r"^(s_call_b64 s\[\d+:\d+\]), .*", r"\1, <target>", ins)
         cur.append(ins)
+    for body in out.values():   # alignment padding in front of the next symbol: it moves with the function's address
+        while body and body[-1] in ("s_nop 0", "...", "s_code_end"):
+            body.pop()
     return out
 
 

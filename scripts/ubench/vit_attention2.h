@@ -1,4 +1,6 @@
 // vit_attention2.h -- flash attention for d_head = 64, second generation (round 2; operand type a parameter since round 3).
+// The library's kernel of rounds 2-3; it left libdtk.so and is kept here for attn_bench.hip only (no test runs it).  It builds on
+// dino_tracker_amd/csrc/vit_attention_common.h (-I dino_tracker_amd/csrc).
 //
 // What changed against attention_kernel (round 1), and why (profiles/r01_bench_kernel_trace.md: 0.37 of the MFMA peak):
 //   * 8 (or 16) waves per CU instead of 4: a workgroup is 512 threads = 8 waves x 32 queries, compiled for <= 128 VGPRs so
@@ -28,7 +30,7 @@ constexpr int NBUF = 3;   // LDS buffers
 
 // QT: 32-query tiles per wave (1: 256 queries per workgroup, <= 128 VGPRs; 2: 512 queries, <= 256 VGPRs)
 // grid: attention_grid(FH, S, 256 * QT, &QB)
-// ABL: ablation switches of the micro-benchmark (scripts/ubench/attn_bench.hip); 0 in the library.
+// ABL: ablation switches of the micro-benchmark (scripts/ubench/attn_bench.hip); 0 = the form the library ran.
 //   1: no exponentials (p = score * c)   2: no LDS-DMA after the first two tiles   4: every fragment read hits ONE LDS address
 //   8: no row maximum / deferred-max logic  16: no barrier
 // MODE 0: running maximum per tile (deferred rescale, threshold 8), as in round 1.
@@ -48,7 +50,7 @@ constexpr int NBUF = 3;   // LDS buffers
 //   (< LOW_T) sum at the end redoes its queries in a safe pass (running maximum per tile, operands read straight from
 //   global memory, no barriers).  The reference never exceeds the row maximum by more than 6 binades (a rescale sets it to
 //   floor(log2(tile sum)) <= log2(64 p_max)), so p_max >= 2^-6 and the entries that matter at 11 bits are normal numbers.
-//   tests/test_gpu_p1.py forces all of these events.
+//   (tests/test_gpu_p1.py forces all of these events on the library's kernels, which use the same arithmetic.)
 template <typename T, int QT, int ABL = 0, int MODE = 1, bool PIN = true, bool PRIO = false>
 __global__ __launch_bounds__(512, QT == 1 ? 4 : 2) void attention2_kernel(const T* __restrict__ Q, const T* __restrict__ Kg,
                                                                           const T* __restrict__ Vt, T* __restrict__ O, int S,

@@ -173,10 +173,27 @@ def test_vit_flag_values_match_header():
     import os
     text = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "dtk.h")).read()
     want = {"DTK_VIT_TILED_GEMMS": _lib.VIT_TILED_GEMMS, "DTK_VIT_BF16": _lib.VIT_BF16, "DTK_VIT_CHECK_RANGE": _lib.VIT_CHECK_RANGE,
-            "DTK_VIT_ATTENTION_V2": _lib.VIT_ATTENTION_V2, "DTK_VIT_GEMM_WS_V1": _lib.VIT_GEMM_WS_V1,
+            "DTK_VIT_GEMM_WS_V1": _lib.VIT_GEMM_WS_V1,
             "DTK_VIT_ATTENTION_V4": _lib.VIT_ATTENTION_V4, "DTK_VIT_GEMM_WIDE_V1": _lib.VIT_GEMM_WIDE_V1,
             "DTK_VIT_NO_LN_FUSION": _lib.VIT_NO_LN_FUSION}
     for name, value in want.items():
         m = re.search(rf"#define {name} (\d+)", text)
         assert m and int(m.group(1)) == value, name
     assert len(set(want.values())) == len(want) and all(v & (v - 1) == 0 for v in want.values())
+
+
+def test_retired_attention_selections_are_refused(handle):
+    """The attention kernels of rounds 2-3 and the round-5 experiment left the library: the bits that selected them are errors, not silent runs on another
+    kernel.  dtk_vit_attention refuses 0x100 .. 0x1000 in operand_type, dtk_vit_forward refuses flags = 8 (and any bit
+    include/dtk.h does not define).  Both checks come before any device call and before any pointer is read, so the dummy
+    (non-null, never dereferenced) pointers below are enough and no device is touched."""
+    buf = ctypes.create_string_buffer(64)
+    p = ctypes.cast(buf, ctypes.c_void_p)
+    for bit in (0x100, 0x200, 0x400, 0x800, 0x1000):
+        rc = handle.dtk_vit_attention(p, p, p, p, 1, 6, 1000, 1024, _lib.OPERAND_F16 | bit, None)
+        assert rc == -1 and b"operand_type" in handle.dtk_last_error(), hex(bit)
+    m = _lib.VitModel()
+    layers = (_lib.VitLayer * 1)()
+    m.D, m.heads, m.depth, m.patch, m.stride, m.flags, m.layers = 384, 6, 1, 14, 7, 8, layers
+    rc = handle.dtk_vit_forward(ctypes.byref(m), p, 1, 140, 210, p, p, p, p, 64, None)
+    assert rc == -1 and b"unknown flag bits 0x8" in handle.dtk_last_error()
