@@ -208,6 +208,14 @@ SIGNATURES = {
     "dtk_flow_traj_start": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p,
                                     c_void_p, c_int, c_float, c_void_p, c_void_p, c_size_t, c_void_p]),
     "dtk_flow_traj_emit": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "dtk_render_prim_count": (ctypes.c_int64, [c_int, c_int, c_int, c_int]),
+    "dtk_render_group_bytes": (c_size_t, [ctypes.c_int64, ctypes.c_int64, c_int, c_int, c_int]),
+    "dtk_render_prims": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                 c_float, c_float, c_int, c_void_p, c_void_p]),
+    "dtk_render_tile_counts": (c_int, [c_void_p, ctypes.c_int64, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "dtk_render_tile_keys": (c_int, [c_void_p, c_void_p, ctypes.c_int64, c_int, c_int, c_int, ctypes.c_int64, c_void_p, c_void_p]),
+    "dtk_render_blend": (c_int, [c_void_p, c_void_p, ctypes.c_int64, c_void_p, ctypes.c_int64, c_void_p, c_int, c_int, c_int,
+                                 c_void_p, c_void_p, c_void_p]),
 }
 
 _LIB = None

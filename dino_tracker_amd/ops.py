@@ -626,3 +626,117 @@ def contrastive_backward(fe: torch.Tensor, a: torch.Tensor, fidx: torch.Tensor, 
                                          _p(nf, torch.float32), _p(na, torch.float32), _p(S, torch.float32), _p(lse, torch.float32),
                                          _p(g, torch.float32), _p(da), _p(dfe), _p(ws), nbytes, _stream()))
     return da, dfe
+
+
+# ---- track videos (csrc/render.hip, docs/RENDER.md): primitives -> tile counts -> keys -> (torch.sort) -> blend --------------------
+RENDER_SEGMENT, RENDER_DISC, RENDER_DIAMOND = 0, 1, 2
+RENDER_DOTTED, RENDER_TAILS = 0, 1
+RENDER_RECORD_WORDS, RENDER_TILE, RENDER_CHUNK = 12, 16, 256
+
+
+def _render_frames(frames: torch.Tensor) -> Tuple[int, int, int]:
+    if frames.dim() != 4 or frames.shape[-1] != 3 or frames.numel() == 0:
+        raise RuntimeError(f"dino_tracker_amd: frames must be [F, H, W, 3] uint8, got {tuple(frames.shape)}")
+    return int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
+
+
+def _render_records(records: torch.Tensor) -> int:
+    if records.dim() != 2 or records.shape[1] != RENDER_RECORD_WORDS:
+        raise RuntimeError(f"dino_tracker_amd: records must be [P, {RENDER_RECORD_WORDS}] float32, got {tuple(records.shape)}")
+    return int(records.shape[0])
+
+
+def render_prim_count(mode: int, N: int, f0: int, F: int) -> int:
+    return int(lib().dtk_render_prim_count(int(mode), int(N), int(f0), int(F)))
+
+
+def render_group_bytes(prims: int, keys: int, F: int, H: int, W: int) -> int:
+    """dtk_render_group_bytes: device bytes of one frame group's buffers (0 for sizes the library refuses)."""
+    return int(lib().dtk_render_group_bytes(int(prims), int(keys), int(F), int(H), int(W)))
+
+
+def render_prims(points: torch.Tensor, occluded: torch.Tensor, colors: torch.Tensor, maps: Optional[torch.Tensor], f0: int, F: int,
+                 H: int, W: int, mode: int, marker_kind: int, marker_size: float, half_width: float = 0.0,
+                 trail_fade: bool = True) -> torch.Tensor:
+    """dtk_render_prims: the records [P, 12] of frames f0 .. f0 + F - 1, in draw order.  points [N, T, 2] fp32, occluded [N, T]
+    uint8, colors [N, 3] fp32, maps [T, T, 9] fp32 (maps[i][j] = inv(H_i) H_j) for RENDER_TAILS."""
+    if points.dim() != 3 or points.shape[2] != 2 or points.shape[0] == 0:
+        raise RuntimeError(f"dino_tracker_amd: points must be [N > 0, T, 2], got {tuple(points.shape)}")
+    N, T = int(points.shape[0]), int(points.shape[1])
+    if tuple(occluded.shape) != (N, T) or tuple(colors.shape) != (N, 3):
+        raise RuntimeError(f"dino_tracker_amd: occluded {tuple(occluded.shape)} / colors {tuple(colors.shape)} do not fit "
+                           f"points {tuple(points.shape)}")
+    if maps is not None and tuple(maps.shape) != (T, T, 9):
+        raise RuntimeError(f"dino_tracker_amd: maps must be [{T}, {T}, 9], got {tuple(maps.shape)}")
+    P = render_prim_count(mode, N, f0, F)
+    records = torch.empty((max(P, 0), RENDER_RECORD_WORDS), dtype=torch.float32, device=points.device)
+    check(lib().dtk_render_prims(_p(points, torch.float32), _p(occluded, torch.uint8), _p(maps, torch.float32),
+                                 _p(colors, torch.float32), N, T, int(f0), int(F), int(H), int(W), int(mode), int(marker_kind),
+                                 float(marker_size), float(half_width), int(bool(trail_fade)), _p(records), _stream()))
+    return records
+
+
+def render_tile_counts(records: torch.Tensor, F: int, H: int, W: int) -> torch.Tensor:
+    """dtk_render_tile_counts: int32 [P], the number of 16 x 16 tiles each record's grown bounding box meets."""
+    P = _render_records(records)
+    counts = torch.empty(P, dtype=torch.int32, device=records.device)
+    check(lib().dtk_render_tile_counts(_p(records, torch.float32), P, int(F), int(H), int(W), _p(counts), _stream()))
+    return counts
+
+
+def render_tile_keys(records: torch.Tensor, offsets: torch.Tensor, K: int, F: int, H: int, W: int) -> torch.Tensor:
+    """dtk_render_tile_keys: int64 [K] keys (frame, tile) << 32 | record, unsorted; offsets = exclusive prefix sum of the counts."""
+    P = _render_records(records)
+    if tuple(offsets.shape) != (P,):
+        raise RuntimeError(f"dino_tracker_amd: offsets must be [{P}], got {tuple(offsets.shape)}")
+    keys = torch.empty(int(K), dtype=torch.int64, device=records.device)
+    check(lib().dtk_render_tile_keys(_p(records, torch.float32), _p(offsets, torch.int64), P, int(F), int(H), int(W), int(K),
+                                     _p(keys), _stream()))
+    return keys
+
+
+def render_tile_starts(sorted_keys: torch.Tensor, F: int, H: int, W: int) -> torch.Tensor:
+    """int64 [F tiles + 1]: the first sorted key of every (frame, tile), by torch.searchsorted (plumbing)."""
+    tiles = F * ((H + RENDER_TILE - 1) // RENDER_TILE) * ((W + RENDER_TILE - 1) // RENDER_TILE)
+    bounds = torch.arange(tiles + 1, dtype=torch.int64, device=sorted_keys.device) << 32
+    return torch.searchsorted(sorted_keys, bounds).contiguous()
+
+
+def render_blend(frames: torch.Tensor, records: torch.Tensor, sorted_keys: torch.Tensor, tile_start: torch.Tensor,
+                 want_float: bool = False) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """dtk_render_blend: (uint8 [F, H, W, 3], fp32 [F, H, W, 3] or None)."""
+    F, H, W = _render_frames(frames)
+    P = _render_records(records)
+    tiles = F * ((H + RENDER_TILE - 1) // RENDER_TILE) * ((W + RENDER_TILE - 1) // RENDER_TILE)
+    if tuple(tile_start.shape) != (tiles + 1,):
+        raise RuntimeError(f"dino_tracker_amd: tile_start must be [{tiles + 1}], got {tuple(tile_start.shape)}")
+    out = torch.empty_like(frames)
+    outf = torch.empty(frames.shape, dtype=torch.float32, device=frames.device) if want_float else None
+    K = int(sorted_keys.numel())
+    check(lib().dtk_render_blend(_p(frames, torch.uint8), _p(records, torch.float32) if P else None, P,
+                                 _p(sorted_keys, torch.int64) if K else None, K, _p(tile_start, torch.int64), F, H, W, _p(out),
+                                 _p(outf), _stream()))
+    return out, outf
+
+
+def render_records(frames: torch.Tensor, records: torch.Tensor, want_float: bool = False,
+                   stats: Optional[dict] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """One frame group through bin / sort / blend.  ONE host read-back: the total key count K (the size of the key array; the
+    same kind of read-back as the compacted row counts of model_inference.py).  torch.cumsum, torch.sort and torch.searchsorted
+    are the plumbing between the stages."""
+    F, H, W = _render_frames(frames)
+    P = _render_records(records)
+    _p(frames, torch.uint8)
+    if P:
+        counts = render_tile_counts(records, F, H, W)
+        ends = torch.cumsum(counts, 0, dtype=torch.int64)
+        K = int(ends[-1].item())                      # the read-back
+        keys = render_tile_keys(records, (ends - counts).contiguous(), K, F, H, W)
+        sorted_keys = torch.sort(keys).values if K else keys
+    else:
+        K, sorted_keys = 0, torch.empty(0, dtype=torch.int64, device=frames.device)
+    if stats is not None:
+        stats["prims"] = stats.get("prims", 0) + P
+        stats["keys"] = stats.get("keys", 0) + K
+        stats["groups"] = stats.get("groups", 0) + 1
+    return render_blend(frames, records, sorted_keys, render_tile_starts(sorted_keys, F, H, W), want_float)

@@ -22,7 +22,8 @@ import sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OVERLAY = os.path.join(REPO, "overlay")
 HOT_MODULES = ("models.tracker", "models.model_inference", "models.extractor", "models.networks.tracker_head",
-               "models.networks.delta_dino", "models.networks.conv_norm", "data.dataset", "utils")
+               "models.networks.delta_dino", "models.networks.conv_norm", "data.dataset", "utils",
+               "visualization.viz_utils_tapir")
 
 
 def _usage() -> "NoReturn":

@@ -665,6 +665,51 @@ int dtk_flow_traj_start(const float* fflow_packed, const float* bflow_packed, co
 int dtk_flow_traj_emit(int32_t T, int32_t h, int32_t w, int32_t s, int32_t min_trajectory_length, int32_t n_rows, float* rows,
                        uint8_t* visited, const void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Track videos: dotted tracks and rainbow trails (visualization/viz_utils_tapir.py plot_tracks_v2 / plot_tracks_tails) as a
+ * tiled, ordered alpha-blending rasteriser.  The picture is DEFINED in docs/RENDER.md (pixel centres, analytic one-pixel coverage
+ * ramps, c <- c (1 - a cov) + colour a cov in fp32, draw order = the reference's); it is not matplotlib's Agg output. -----------
+ * A primitive RECORD is DTK_RENDER_RECORD_WORDS = 12 32-bit words:
+ *   [0] kind (int32: DTK_RENDER_SEGMENT / _DISC / _DIAMOND)   [1..4] x0 y0 x1 y1 (markers: both ends the centre)
+ *   [5] size: half-width (segment), radius (disc), L1 radius rho (diamond)       [6..8] r g b in [0, 1]      [9] a
+ *   [10] 1 / |p1 - p0|^2 (0 for a zero-length segment and for markers)           [11] frame in the group (int32)
+ * Records are stored in draw order: frame by frame, and within a frame in the order the reference draws.
+ *
+ * dtk_render_prims writes the records of frames f0 .. f0 + F - 1 of a video of T frames with N points.  points [N][T][2] fp32,
+ *   occluded [N][T] uint8 (0 / 1), colors [N][3] fp32.  mode DTK_RENDER_DOTTED: N markers per frame, a = 1 - occluded[n][i].
+ *   mode DTK_RENDER_TAILS: maps [T][T][9] fp32 with maps[i][j] = inv(H_i) H_j (row-major 3 x 3, formed by the caller in float64;
+ *   only j < i is read); frame i has N (i + 1) records: the markers, then for j = i - 1 .. 0 the N segments P(n, j) -> P(n, j + 1)
+ *   with the reference's out-of-frame rule, clamping and fade (docs/RENDER.md).  A record with a = 0 bins nowhere.
+ *   dtk_render_prim_count(mode, N, f0, F) is the number of records of the group.
+ * dtk_render_tile_counts: counts[p] = number of DTK_RENDER_TILE x DTK_RENDER_TILE tiles the bounding box of record p meets: the
+ *   extent grown by size + 0.5 (diamond: size + sqrt(1/2)), clipped to the W x H frame; 0 when a <= 0, a coordinate is not finite or the record's frame is not in 0 .. F - 1.
+ * dtk_render_tile_keys: offsets[p] = exclusive prefix sum of counts (int64); writes one key per (tile, record):
+ *   key = ((frame * tiles_y + ty) * tiles_x + tx) << 32 | p.  Keys are unique, so their sorted order does not depend on which
+ *   thread wrote which; ascending order inside one (frame, tile) is draw order.
+ * dtk_render_blend: sorted keys [K], tile_start [F tiles_y tiles_x + 1] (tile_start[t] = first key of tile t, = searchsorted of
+ *   t << 32).  One workgroup of 256 threads per tile, one pixel per thread; the tile's records pass through LDS in chunks of
+ *   DTK_RENDER_CHUNK.  frames_in [F][H][W][3] uint8 -> out_u8 [F][H][W][3] uint8 = floor(255 c + 0.5), and out_f32 (same shape,
+ *   fp32 c) when not null.  Only plain vector stores; no atomics anywhere, so two calls give the same bits.
+ * dtk_render_group_bytes: device bytes of one frame group's buffers (records, counts, offsets, keys and their sort, tile starts,
+ *   input and output frames) for `prims` records and `keys` keys; the caller sizes its frame groups with it.  0 for bad sizes. */
+#define DTK_RENDER_SEGMENT 0
+#define DTK_RENDER_DISC 1
+#define DTK_RENDER_DIAMOND 2
+#define DTK_RENDER_DOTTED 0
+#define DTK_RENDER_TAILS 1
+#define DTK_RENDER_RECORD_WORDS 12
+#define DTK_RENDER_TILE 16
+#define DTK_RENDER_CHUNK 256
+int64_t dtk_render_prim_count(int32_t mode, int32_t N, int32_t f0, int32_t F);
+size_t dtk_render_group_bytes(int64_t prims, int64_t keys, int32_t F, int32_t H, int32_t W);
+int dtk_render_prims(const float* points, const uint8_t* occluded, const float* maps, const float* colors, int32_t N, int32_t T,
+                     int32_t f0, int32_t F, int32_t H, int32_t W, int32_t mode, int32_t marker_kind, float marker_size,
+                     float half_width, int32_t trail_fade, float* records, void* stream);
+int dtk_render_tile_counts(const float* records, int64_t P, int32_t F, int32_t H, int32_t W, int32_t* counts, void* stream);
+int dtk_render_tile_keys(const float* records, const int64_t* offsets, int64_t P, int32_t F, int32_t H, int32_t W, int64_t K,
+                         int64_t* keys, void* stream);
+int dtk_render_blend(const uint8_t* frames_in, const float* records, int64_t P, const int64_t* sorted_keys, int64_t K,
+                     const int64_t* tile_start, int32_t F, int32_t H, int32_t W, uint8_t* out_u8, float* out_f32, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
