@@ -255,11 +255,12 @@ extern "C" int dtk_tapvid_counts(const float* pred_tracks, const uint8_t* pred_o
                                  const uint8_t* gt_occluded, const int32_t* query_frame, float pred_scale_x,
                                  float pred_scale_y, float gt_scale_x, float gt_scale_y, int first_mode, int N, int T,
                                  unsigned long long* counts18, void* stream) {
-    DTK_REQUIRE(pred_tracks && pred_occluded && gt_tracks && gt_occluded && query_frame && counts18, "dtk_tapvid_counts: null pointer");
+    DTK_REQUIRE(counts18, "dtk_tapvid_counts: null pointer");
     DTK_REQUIRE(N >= 0 && T > 0, "dtk_tapvid_counts: bad sizes");
     hipStream_t st = dtk_stream(stream);
     DTK_HIP(hipMemsetAsync(counts18, 0, 18 * sizeof(unsigned long long), st));
-    if (N == 0) return DTK_OK;
+    if (N == 0) return DTK_OK;  // no query: eighteen zeros (the arrays are empty, and an empty device tensor has no address)
+    DTK_REQUIRE(pred_tracks && pred_occluded && gt_tracks && gt_occluded && query_frame, "dtk_tapvid_counts: null pointer");
     DTK_LAUNCH("tapvid_counts", tapvid_counts_kernel, dim3(dtk_cdiv((long long)N * T, 256)), dim3(256), 0, st, pred_tracks,
                pred_occluded, gt_tracks, gt_occluded, query_frame, pred_scale_x, pred_scale_y, gt_scale_x, gt_scale_y,
                first_mode, N, T, counts18);
