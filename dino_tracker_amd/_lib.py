@@ -176,6 +176,8 @@ SIGNATURES = {
                               c_int, c_void_p]),
     "dtk_tapvid_counts": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float,
                                   c_int, c_int, c_int, c_void_p, c_void_p]),
+    "dtk_badja_counts": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float, c_float, c_int, c_int, c_int, c_int, c_int,
+                                 c_void_p, c_void_p, c_void_p]),
     "dtk_blurpool_forward": (c_int, [c_void_p, c_void_p, ctypes.c_int64, c_int, c_int, c_void_p]),
     "dtk_blurpool_backward": (c_int, [c_void_p, c_void_p, ctypes.c_int64, c_int, c_int, c_void_p]),
     "dtk_gemm_nt_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
@@ -212,6 +214,8 @@ SIGNATURES = {
     "dtk_render_group_bytes": (c_size_t, [ctypes.c_int64, ctypes.c_int64, c_int, c_int, c_int]),
     "dtk_render_prims": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                  c_float, c_float, c_int, c_void_p, c_void_p]),
+    "dtk_render_pred_gt_prims": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                         c_int, c_int, c_void_p, c_void_p]),
     "dtk_render_tile_counts": (c_int, [c_void_p, ctypes.c_int64, c_int, c_int, c_int, c_void_p, c_void_p]),
     "dtk_render_tile_keys": (c_int, [c_void_p, c_void_p, ctypes.c_int64, c_int, c_int, c_int, ctypes.c_int64, c_void_p, c_void_p]),
     "dtk_render_blend": (c_int, [c_void_p, c_void_p, ctypes.c_int64, c_void_p, ctypes.c_int64, c_void_p, c_int, c_int, c_int,

@@ -266,3 +266,82 @@ extern "C" int dtk_tapvid_counts(const float* pred_tracks, const uint8_t* pred_o
                first_mode, N, T, counts18);
     return DTK_OK;
 }
+
+
+// ------------------------------------------------------------------------------------------------------------
+// BADJA metric counts on the device (eval/metrics.py:226-287, compute_badja_metrics_for_video for ONE video).
+//   area[t]  = number of segmentations[t] > 0 pixels (an integer; numpy's float32 sum of 0 / 1 flags is the same number while it
+//              stays below 2^24, which the launcher guarantees by refusing H W >= 2^24)
+//   thr[t]   = float32(0.2) * sqrtf(float32(area[t]))          (what numpy 2 computes: the python float 0.2 is a weak scalar)
+//   for every point i and frame t in 1 .. T_seg - 1 with gt_occluded[i][t] == 0:
+//     dist = sqrt((px - gx)^2 + (py - gy)^2) in float64, px = float32(pred * scale) promoted, gx the float64 ground truth,
+//     the sum not contracted into an FMA
+//   counts3 (uint64): [0] visible  [1] dist < thr[t]  [2] dist < 3.0
+// Integer atomics only, so two calls give the same bits.
+// ------------------------------------------------------------------------------------------------------------
+template <typename M>
+__global__ __launch_bounds__(256) void badja_area_kernel(const M* __restrict__ seg, long long HW,
+                                                         unsigned long long* __restrict__ areas) {
+    const M* frame = seg + (size_t)blockIdx.y * HW;
+    int c = 0;   // at most HW / gridDim.x / 256 + 1 < 2^24 per thread
+    for (long long p = (long long)blockIdx.x * 256 + threadIdx.x; p < HW; p += (long long)gridDim.x * 256) c += frame[p] > (M)0;
+    c = wave_sum_i(c);
+    if ((threadIdx.x & 63) == 0 && c) atomicAdd(&areas[blockIdx.y], (unsigned long long)c);
+}
+
+__global__ __launch_bounds__(256) void badja_counts_kernel(const float* __restrict__ pred, const double* __restrict__ gt,
+                                                           const uint8_t* __restrict__ gt_occ,
+                                                           const unsigned long long* __restrict__ areas, float spx, float spy,
+                                                           int N, int T, int T_seg, unsigned long long* __restrict__ counts) {
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    const int per = T_seg - 1;   // frames 1 .. T_seg - 1
+    int vis = 0, in_seg = 0, in_3px = 0;
+    if (idx < (long long)N * per) {
+        const int n = (int)(idx / per), t = 1 + (int)(idx - (long long)n * per);
+        const size_t at = (size_t)n * T + t;
+        if (gt_occ[at] == 0) {
+            const float thr = __fmul_rn(0.2f, __fsqrt_rn((float)areas[t]));
+            const double dx = __dsub_rn((double)__fmul_rn(pred[2 * at], spx), gt[2 * at]);
+            const double dy = __dsub_rn((double)__fmul_rn(pred[2 * at + 1], spy), gt[2 * at + 1]);
+            const double dist = __dsqrt_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)));
+            vis = 1;
+            in_seg = dist < (double)thr;
+            in_3px = dist < 3.0;
+        }
+    }
+    vis = wave_sum_i(vis), in_seg = wave_sum_i(in_seg), in_3px = wave_sum_i(in_3px);
+    if ((threadIdx.x & 63) == 0) {
+        if (vis) atomicAdd(&counts[0], (unsigned long long)vis);
+        if (in_seg) atomicAdd(&counts[1], (unsigned long long)in_seg);
+        if (in_3px) atomicAdd(&counts[2], (unsigned long long)in_3px);
+    }
+}
+
+extern "C" int dtk_badja_counts(const float* pred_tracks, const double* gt_tracks, const uint8_t* gt_occluded,
+                                const void* segmentations, int32_t seg_is_float, float pred_scale_x, float pred_scale_y,
+                                int32_t N, int32_t T, int32_t T_seg, int32_t H, int32_t W, unsigned long long* areas,
+                                unsigned long long* counts3, void* stream) {
+    DTK_REQUIRE(counts3 && areas && segmentations, "dtk_badja_counts: null pointer");
+    DTK_REQUIRE(N >= 0 && T > 0 && T_seg > 0 && T_seg <= T && T_seg <= 65535 && H > 0 && W > 0,
+                "dtk_badja_counts: bad sizes N=%d T=%d T_seg=%d (needs 1 <= T_seg <= T) masks %d x %d", N, T, T_seg, W, H);
+    DTK_REQUIRE((long long)H * W < (1LL << 24),
+                "dtk_badja_counts: a %d x %d mask can have an area of 2^24 or more, where numpy's float32 sum of the reference "
+                "stops being the pixel count", W, H);
+    DTK_REQUIRE(seg_is_float == 0 || seg_is_float == 1, "dtk_badja_counts: seg_is_float must be 0 (uint8) or 1 (float32)");
+    hipStream_t st = dtk_stream(stream);
+    DTK_HIP(hipMemsetAsync(counts3, 0, 3 * sizeof(unsigned long long), st));
+    DTK_HIP(hipMemsetAsync(areas, 0, (size_t)T_seg * sizeof(unsigned long long), st));
+    const long long HW = (long long)H * W;
+    const int per_frame = dtk_cdiv(HW, 256 * 8);   // blocks per mask: about eight pixels per thread
+    const dim3 grid(per_frame < 1024 ? per_frame : 1024, T_seg);
+    if (seg_is_float) {
+        DTK_LAUNCH("badja_area", badja_area_kernel<float>, grid, dim3(256), 0, st, (const float*)segmentations, HW, areas);
+    } else {
+        DTK_LAUNCH("badja_area", badja_area_kernel<uint8_t>, grid, dim3(256), 0, st, (const uint8_t*)segmentations, HW, areas);
+    }
+    if (N == 0 || T_seg == 1) return DTK_OK;   // nothing to score: three zeros
+    DTK_REQUIRE(pred_tracks && gt_tracks && gt_occluded, "dtk_badja_counts: null pointer");
+    DTK_LAUNCH("badja_counts", badja_counts_kernel, dim3(dtk_cdiv((long long)N * (T_seg - 1), 256)), dim3(256), 0, st, pred_tracks,
+               gt_tracks, gt_occluded, areas, pred_scale_x, pred_scale_y, N, T, T_seg, counts3);
+    return DTK_OK;
+}

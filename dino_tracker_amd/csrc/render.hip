@@ -3,6 +3,8 @@
 // the stages, one export each (include/dtk.h):
 //
 //   dtk_render_prims       : one thread per (frame, j, n) writes the 48-byte record of one primitive, in draw order
+//   dtk_render_pred_gt_prims : one thread per (frame, n) writes the two records of a prediction-against-ground-truth point
+//                            (visualization/visualize_pred_vs_gt.py:13-38): displacement line + disc, cross, or line + ring
 //   dtk_render_tile_counts : per record, the number of 16 x 16 tiles its grown bounding box meets
 //   dtk_render_tile_keys   : per (tile, record) one 64-bit key  (frame, tile) << 32 | record index  at the record's offset in the
 //                            exclusive prefix sum of the counts.  The caller sorts the keys; they are unique, so the sorted
@@ -89,6 +91,44 @@ __global__ __launch_bounds__(RTHREADS) void render_prims_kernel(const float* __r
     store_record(rec, DTK_RENDER_SEGMENT, p0.x, p0.y, p1.x, p1.y, half_width, col, a, len2 > 0.f ? 1.f / len2 : 0.f, fi);
 }
 
+// overlay_pred_gt_on_frame (visualize_pred_vs_gt.py:21-38) on integer points: exactly two records per (frame, point)
+__global__ __launch_bounds__(RTHREADS) void render_pred_gt_prims_kernel(const int32_t* __restrict__ pred_xy,
+                                                                        const int32_t* __restrict__ gt_xy,
+                                                                        const uint8_t* __restrict__ pred_occ,
+                                                                        const uint8_t* __restrict__ gt_occ,
+                                                                        const float* __restrict__ colors, int N, int T, int f0,
+                                                                        int thickness, int radius, int cross_size,
+                                                                        float* __restrict__ records) {
+    const int fi = blockIdx.y, i = f0 + fi;
+    const int n = blockIdx.x * RTHREADS + threadIdx.x;
+    if (n >= N) return;
+    const size_t at = (size_t)n * T + i;
+    float* rec = records + ((size_t)fi * N + n) * 2 * RW;
+    const float* col = colors + (size_t)n * 3;
+    const float red[3] = {1.f, 0.f, 0.f};
+    const float px = (float)pred_xy[2 * at], py = (float)pred_xy[2 * at + 1];
+    const float gx = (float)gt_xy[2 * at], gy = (float)gt_xy[2 * at + 1];
+    const bool pocc = pred_occ[at] != 0, gocc = gt_occ[at] != 0;
+    if (pocc && gocc) {   // drawn nowhere: two records with a = 0
+        const float none[3] = {0.f, 0.f, 0.f};
+        store_record(rec, DTK_RENDER_SEGMENT, 0.f, 0.f, 0.f, 0.f, 0.f, none, 0.f, 0.f, fi);
+        store_record(rec + RW, DTK_RENDER_SEGMENT, 0.f, 0.f, 0.f, 0.f, 0.f, none, 0.f, 0.f, fi);
+        return;
+    }
+    if (!pocc && gocc) {   // the cross: two diagonals of +- cross_size
+        const float r = (float)cross_size, hw = (float)thickness * 0.5f;
+        const float len2 = 8.f * r * r, inv = len2 > 0.f ? __fdiv_rn(1.f, len2) : 0.f;
+        store_record(rec, DTK_RENDER_SEGMENT, px - r, py - r, px + r, py + r, hw, col, 1.f, inv, fi);
+        store_record(rec + RW, DTK_RENDER_SEGMENT, px - r, py + r, px + r, py - r, hw, col, 1.f, inv, fi);
+        return;
+    }
+    const float dx = gx - px, dy = gy - py, len2 = __fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy));   // as numpy: no FMA
+    const float hw = (float)(pocc ? thickness / 2 : thickness) * 0.5f;   // cv2 thickness // 2 where the prediction is occluded
+    store_record(rec, DTK_RENDER_SEGMENT, px, py, gx, gy, hw, red, 1.f, len2 > 0.f ? __fdiv_rn(1.f, len2) : 0.f, fi);
+    if (pocc) store_record(rec + RW, DTK_RENDER_RING, px, py, px, py, (float)radius, col, 1.f, 1.f, fi);   // word [10]: hw = 1
+    else store_record(rec + RW, DTK_RENDER_DISC, px, py, px, py, (float)radius, col, 1.f, 0.f, fi);
+}
+
 struct TileBox {
     int tx0, tx1, ty0, ty1, frame;
     __device__ int count() const { return (tx1 - tx0 + 1) * (ty1 - ty0 + 1); }
@@ -104,7 +144,11 @@ __device__ __forceinline__ bool tile_box(const float* __restrict__ rec, int F, i
     b.frame = __float_as_int(q2.w);
     if (!(a > 0.f) || b.frame < 0 || b.frame >= F) return false;
     if (!(isfinite(x0) && isfinite(y0) && isfinite(x1) && isfinite(y1) && isfinite(size))) return false;
-    const float grow = size + (kind == DTK_RENDER_DIAMOND ? 0.70711f : 0.5f);   // coverage is 0 beyond it (docs/RENDER.md)
+    float grow = size + (kind == DTK_RENDER_DIAMOND ? 0.70711f : 0.5f);   // coverage is 0 beyond it (docs/RENDER.md)
+    if (kind == DTK_RENDER_RING) {   // the stroke reaches r + hw; word [10] is its half width
+        if (!isfinite(q2.z)) return false;
+        grow += q2.z;
+    }
     const float xmin = fminf(x0, x1) - grow, xmax = fmaxf(x0, x1) + grow;
     const float ymin = fminf(y0, y1) - grow, ymax = fmaxf(y0, y1) + grow;
     if (!(xmax >= 0.f && ymax >= 0.f && xmin <= (float)(W - 1) && ymin <= (float)(H - 1))) return false;
@@ -178,6 +222,8 @@ __global__ __launch_bounds__(RTHREADS) void render_blend_kernel(const uint8_t* _
                 float cov;
                 if (kind == DTK_RENDER_DIAMOND) {
                     cov = 0.5f + (q1.y - fabsf(ax) - fabsf(ay)) / 1.41421356237f;
+                } else if (kind == DTK_RENDER_RING) {
+                    cov = 0.5f + q2.z - fabsf(sqrtf(ax * ax + ay * ay) - q1.y);
                 } else {   // a disc is a zero-length segment
                     const float dx = q0.w - q0.y, dy = q1.x - q0.z;
                     float t = (ax * dx + ay * dy) * q2.z;
@@ -283,5 +329,22 @@ extern "C" int dtk_render_blend(const uint8_t* frames_in, const float* records, 
     DTK_REQUIRE(K == 0 || (records && sorted_keys), "render_blend: K=%lld keys but no records / keys", (long long)K);
     DTK_LAUNCH("render_blend", render_blend_kernel, dim3(dtk_cdiv(W, RT), dtk_cdiv(H, RT), F), dim3(RTHREADS), 0,
                dtk_stream(stream), frames_in, records, (long long)P, sorted_keys, (long long)K, tile_start, H, W, out_u8, out_f32);
+    return 0;
+}
+
+extern "C" int dtk_render_pred_gt_prims(const int32_t* pred_xy, const int32_t* gt_xy, const uint8_t* pred_occluded,
+                                        const uint8_t* gt_occluded, const float* colors, int32_t N, int32_t T, int32_t f0,
+                                        int32_t F, int32_t thickness, int32_t radius, int32_t cross_size, float* records,
+                                        void* stream) {
+    DTK_REQUIRE(N > 0 && T > 0 && f0 >= 0 && F > 0 && F <= 65535 && f0 + (long long)F <= T,
+                "render_pred_gt_prims: bad sizes N=%d T=%d frames %d .. %d + %d", N, T, f0, f0, F);
+    DTK_REQUIRE(thickness >= 1 && radius >= 0 && cross_size >= 0 && thickness <= 4096 && radius <= 4096 && cross_size <= 4096,
+                "render_pred_gt_prims: thickness %d must be 1 .. 4096, radius %d and cross_size %d 0 .. 4096", thickness, radius,
+                cross_size);
+    DTK_REQUIRE(2LL * N * F < (1LL << 31), "render_pred_gt_prims: more than 2^31 records in one frame group");
+    DTK_REQUIRE(pred_xy && gt_xy && pred_occluded && gt_occluded && colors && records, "render_pred_gt_prims: null pointer");
+    DTK_LAUNCH("render_pred_gt_prims", render_pred_gt_prims_kernel, dim3(dtk_cdiv(N, RTHREADS), F), dim3(RTHREADS), 0,
+               dtk_stream(stream), pred_xy, gt_xy, pred_occluded, gt_occluded, colors, N, T, f0, thickness, radius, cross_size,
+               records);
     return 0;
 }

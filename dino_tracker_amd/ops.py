@@ -629,7 +629,7 @@ def contrastive_backward(fe: torch.Tensor, a: torch.Tensor, fidx: torch.Tensor, 
 
 
 # ---- track videos (csrc/render.hip, docs/RENDER.md): primitives -> tile counts -> keys -> (torch.sort) -> blend --------------------
-RENDER_SEGMENT, RENDER_DISC, RENDER_DIAMOND = 0, 1, 2
+RENDER_SEGMENT, RENDER_DISC, RENDER_DIAMOND, RENDER_RING = 0, 1, 2, 3
 RENDER_DOTTED, RENDER_TAILS = 0, 1
 RENDER_RECORD_WORDS, RENDER_TILE, RENDER_CHUNK = 12, 16, 256
 
@@ -673,6 +673,25 @@ def render_prims(points: torch.Tensor, occluded: torch.Tensor, colors: torch.Ten
     check(lib().dtk_render_prims(_p(points, torch.float32), _p(occluded, torch.uint8), _p(maps, torch.float32),
                                  _p(colors, torch.float32), N, T, int(f0), int(F), int(H), int(W), int(mode), int(marker_kind),
                                  float(marker_size), float(half_width), int(bool(trail_fade)), _p(records), _stream()))
+    return records
+
+
+def render_pred_gt_prims(pred_xy: torch.Tensor, gt_xy: torch.Tensor, pred_occluded: torch.Tensor, gt_occluded: torch.Tensor,
+                         colors: torch.Tensor, f0: int, F: int, thickness: int = 4, radius: int = 8,
+                         cross_size: int = 8) -> torch.Tensor:
+    """dtk_render_pred_gt_prims: the records [2 N F, 12] of frames f0 .. f0 + F - 1 of a prediction-against-ground-truth video,
+    two per (frame, point).  pred_xy / gt_xy [N, T, 2] int32, pred_occluded / gt_occluded [N, T] uint8, colors [N, 3] fp32."""
+    if pred_xy.dim() != 3 or pred_xy.shape[2] != 2 or pred_xy.shape[0] == 0:
+        raise RuntimeError(f"dino_tracker_amd: pred_xy must be [N > 0, T, 2], got {tuple(pred_xy.shape)}")
+    N, T = int(pred_xy.shape[0]), int(pred_xy.shape[1])
+    if (tuple(gt_xy.shape) != (N, T, 2) or tuple(pred_occluded.shape) != (N, T) or tuple(gt_occluded.shape) != (N, T)
+            or tuple(colors.shape) != (N, 3)):
+        raise RuntimeError(f"dino_tracker_amd: gt_xy {tuple(gt_xy.shape)} / occluded {tuple(pred_occluded.shape)}, "
+                           f"{tuple(gt_occluded.shape)} / colors {tuple(colors.shape)} do not fit pred_xy {tuple(pred_xy.shape)}")
+    records = torch.empty((2 * N * max(int(F), 0), RENDER_RECORD_WORDS), dtype=torch.float32, device=pred_xy.device)
+    check(lib().dtk_render_pred_gt_prims(_p(pred_xy, torch.int32), _p(gt_xy, torch.int32), _p(pred_occluded, torch.uint8),
+                                         _p(gt_occluded, torch.uint8), _p(colors, torch.float32), N, T, int(f0), int(F),
+                                         int(thickness), int(radius), int(cross_size), _p(records), _stream()))
     return records
 
 

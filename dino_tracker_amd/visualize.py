@@ -6,6 +6,12 @@ implementation.
 writes the dotted-track video (plot_tracks_v2) and, with --plot-trails, the camera-stabilised rainbow trails
 (get_homographies_wrt_frame + plot_tracks_tails) into <data-path>/visualizations, the reference's file layout.
 
+    python -m dino_tracker_amd.visualize pred-vs-gt --data-path dataset/tapvid/0 --benchmark-pickle-path davis.pkl --video-id 0
+
+is the reference's visualization/visualize_pred_vs_gt.py without cv2: per start frame of the benchmark one video
+pred_vs_gt_frame_idx_<f>_fps_<fps>.mp4 with displacement lines, discs, rings and crosses (docs/RENDER.md section 5).  The benchmark
+pickle is the user's own file and is UNPICKLED: only give it files you trust.
+
 Two halves:
 
 * The homography estimation (get_homographies_wrt_frame and what it calls) is a float64 numpy restatement with the reference's
@@ -22,6 +28,9 @@ from __future__ import annotations
 import argparse
 import colorsys
 import os
+import pickle
+import random
+import sys
 from pathlib import Path
 from typing import Optional
 
@@ -251,14 +260,15 @@ def _to(x, dev, dtype) -> torch.Tensor:
     return torch.from_numpy(np.ascontiguousarray(np.asarray(x))).to(dev).to(dtype).contiguous()
 
 
-def frame_groups(mode: int, N: int, T: int, H: int, W: int, budget: int = DEFAULT_BUDGET) -> list:
+def frame_groups(mode: int, N: int, T: int, H: int, W: int, budget: int = DEFAULT_BUDGET, prim_count=None) -> list:
     """[(f0, F), ...]: consecutive frame groups whose buffers (dtk_render_group_bytes, with KEYS_PER_PRIM keys per record as the
-    estimate of the key array) fit `budget` bytes; a group holds at least one frame."""
+    estimate of the key array) fit `budget` bytes; a group holds at least one frame.  `prim_count(f0, F)` replaces
+    dtk_render_prim_count(mode, N, f0, F) for videos that are neither of its two modes."""
     groups, f0 = [], 0
     while f0 < T:
         F = 1
         while f0 + F < T:
-            P = ops.render_prim_count(mode, N, f0, F + 1)
+            P = prim_count(f0, F + 1) if prim_count is not None else ops.render_prim_count(mode, N, f0, F + 1)
             need = ops.render_group_bytes(P, KEYS_PER_PRIM * P, F + 1, H, W)
             if need == 0 or need > budget or P >= 1 << 31:
                 break
@@ -332,6 +342,108 @@ def plot_tracks_tails(rgb, points, occluded, homogs, point_size: int = 12, linew
                    trail_fade, group_frames, memory_budget, return_float, stats)
 
 
+# ---- prediction against ground truth (visualization/visualize_pred_vs_gt.py) --------------------------------------------------------
+def get_colors(num_colors: int, seed=0, without_red=False, rng=None) -> list:
+    """viz_utils.py:7-22: one (r, g, b) of ints per point; two draws from `np.random` (or `rng`) per colour, lightness first, then
+    the list is shuffled with random.seed(seed).  Reddish colours (r > 200) lose 100 of red when `without_red`."""
+    rng = np.random if rng is None else rng
+    colors = []
+    for i in np.arange(0.0, 360.0, 360.0 / num_colors):
+        hue = i / 360.0
+        lightness = (50 + rng.rand() * 10) / 100.0
+        saturation = (90 + rng.rand() * 10) / 100.0
+        color = colorsys.hls_to_rgb(hue, lightness, saturation)
+        color = (int(color[0] * 255), int(color[1] * 255), int(color[2] * 255))
+        if without_red and color[0] > 200:
+            color = (color[0] - 100, color[1], color[2])
+        colors.append(color)
+    random.seed(seed)
+    random.shuffle(colors)
+    return colors
+
+
+COORD_LIMIT = 1 << 24   # integer coordinates beyond it are not float32 numbers; such a point is far outside any frame
+
+
+def _int_points(x, dev) -> torch.Tensor:
+    """tuple(point.astype(int)): truncation toward zero in the input's own dtype, as int32 on the device."""
+    if isinstance(x, torch.Tensor):
+        if not x.is_cuda:
+            raise RuntimeError("dino_tracker_amd: tensor is not on a GPU -- the hot path has no CPU fallback")
+        t = torch.nan_to_num(x, nan=0.0) if x.is_floating_point() else x
+        return t.clamp(-COORD_LIMIT, COORD_LIMIT).to(torch.int32).contiguous()
+    a = np.asarray(x)
+    a = np.nan_to_num(a, nan=0.0) if a.dtype.kind == "f" else a
+    return torch.from_numpy(np.clip(a, -COORD_LIMIT, COORD_LIMIT).astype(int).astype(np.int32)).to(dev).contiguous()
+
+
+def badja_frames(gt_trajectories) -> list:
+    """visualize_pred_vs_gt.py:51: the frames where fewer than 60 % of the ground-truth points are (< 1, < 1), BADJA's mark for
+    `not annotated`."""
+    gt = gt_trajectories.detach().cpu().numpy() if isinstance(gt_trajectories, torch.Tensor) else np.asarray(gt_trajectories)
+    return [i for i in range(gt.shape[1]) if ((gt[:, i, :] < 1).all(axis=-1)).mean() < 0.6]
+
+
+def visualize_trajectories_with_gt(video, pred_trajectories, gt_trajectories, pred_occluded=None, gt_occluded=None, thickness=4,
+                                   radius=8, cross_size=8, badja_vis_type=False, *, group_frames: Optional[int] = None,
+                                   memory_budget: int = DEFAULT_BUDGET, return_float: bool = False,
+                                   stats: Optional[dict] = None):
+    """visualize_pred_vs_gt.py:40-67 on the device (docs/RENDER.md section 5).  video [T, H, W, 3] uint8, trajectories [N, T, 2],
+    occlusion flags [N, T] (None: all visible); numpy arrays or device tensors.  Per frame and point, in ascending n: a red line
+    prediction -> ground truth and a disc (both visible), a cross (ground truth occluded), a thin red line and a ring (prediction
+    occluded), nothing (both occluded).  Colours: get_colors(N, seed=0, without_red=True) / 255, which draws from np.random as the
+    reference does.  With `badja_vis_type` only the frames of badja_frames(gt) are rendered.  Returns [T', H, W, 3] uint8 of the
+    kind `video` is (and the float32 picture after it with `return_float`)."""
+    assert tuple(pred_trajectories.shape) == tuple(gt_trajectories.shape), \
+        (f"pred and gt trajectories must be the same shape, pred.shape={tuple(pred_trajectories.shape)}, "
+         f"gt.shape={tuple(gt_trajectories.shape)}")
+    dev = _device_of(video, pred_trajectories, gt_trajectories, pred_occluded, gt_occluded)
+    as_numpy = not isinstance(video, torch.Tensor)
+    if (video.dtype != torch.uint8) if isinstance(video, torch.Tensor) else (np.asarray(video).dtype != np.uint8):
+        raise TypeError("video must be uint8 [T, H, W, 3]")
+    frames = _to(video, dev, torch.uint8)
+    T, H, W = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
+    N = int(pred_trajectories.shape[0])
+    if pred_trajectories.ndim != 3 or pred_trajectories.shape[2] != 2 or pred_trajectories.shape[1] < T:
+        raise RuntimeError(f"trajectories {tuple(pred_trajectories.shape)} do not fit {T} frames")
+    colormap = get_colors(num_colors=N, seed=0, without_red=True) if N else []
+    kept = [i for i in badja_frames(gt_trajectories) if i < T] if badja_vis_type else list(range(T))
+
+    def flags(o):
+        if o is None:
+            return torch.zeros((N, pred_trajectories.shape[1]), dtype=torch.uint8, device=dev)
+        return _to((o != 0) if isinstance(o, torch.Tensor) else (np.asarray(o) != 0), dev, torch.uint8)
+
+    pocc, gocc = flags(pred_occluded), flags(gt_occluded)
+    if tuple(pocc.shape) != tuple(pred_trajectories.shape[:2]) or tuple(gocc.shape) != tuple(pred_trajectories.shape[:2]):
+        raise RuntimeError(f"occlusion flags {tuple(pocc.shape)} / {tuple(gocc.shape)} do not fit trajectories "
+                           f"{tuple(pred_trajectories.shape)}")
+    idx = torch.as_tensor(kept, dtype=torch.long, device=dev)
+    frames = frames.index_select(0, idx).contiguous()
+    K = len(kept)
+    out = frames.clone()
+    outf = (frames.float() / 255.0) if return_float else None
+    if N and K:
+        pxy = _int_points(pred_trajectories, dev).index_select(1, idx).contiguous()
+        gxy = _int_points(gt_trajectories, dev).index_select(1, idx).contiguous()
+        pocc, gocc = pocc.index_select(1, idx).contiguous(), gocc.index_select(1, idx).contiguous()
+        colors = _to(np.asarray(colormap, dtype=np.float64) / 255.0, dev, torch.float32)
+        if group_frames:
+            groups = [(f0, min(int(group_frames), K - f0)) for f0 in range(0, K, int(group_frames))]
+        else:
+            groups = frame_groups(-1, N, K, H, W, memory_budget, prim_count=lambda f0, F: 2 * N * F)
+        for f0, F in groups:   # one read-back per group (ops.render_records: the key count)
+            rec = ops.render_pred_gt_prims(pxy, gxy, pocc, gocc, colors, f0, F, thickness, radius, cross_size)
+            u8, f32 = ops.render_records(frames[f0:f0 + F], rec, return_float, stats)
+            out[f0:f0 + F] = u8
+            if outf is not None:
+                outf[f0:f0 + F] = f32
+    res = out.cpu().numpy() if as_numpy else out
+    if return_float:
+        return res, (outf.cpu().numpy() if as_numpy else outf)
+    return res
+
+
 def save_video(video, path: str, fps: int = 10) -> str:
     """Writes [T, H, W, 3] uint8 as an mp4 through imageio when that imports; otherwise as PNG frames 00000.png ... in a folder
     named like the file without its extension.  Returns what it wrote and says so."""
@@ -356,7 +468,7 @@ def save_video(video, path: str, fps: int = 10) -> str:
     return folder
 
 
-def _load_video_u8(video_folder: str, num_frames: int = 300) -> np.ndarray:
+def _load_video_u8(video_folder: str, num_frames: Optional[int] = 300) -> np.ndarray:
     from PIL import Image
     files = sorted(list(Path(video_folder).glob("*.jpg")) + list(Path(video_folder).glob("*.png")))[:num_frames]
     return np.stack([np.asarray(Image.open(str(f)).convert("RGB")) for f in files])
@@ -416,6 +528,54 @@ def run(args, device: str = "cuda:0"):
     return written
 
 
+@torch.no_grad()
+def save_prediction_vs_gt(args, device: str = "cuda:0"):
+    """visualize_pred_vs_gt.py:70-106 on the layout of utils.add_config_paths: per start frame of the benchmark video one
+    pred_vs_gt_frame_idx_<f>_fps_<fps>.mp4 (or PNG folder, see save_video) in <data-path>/visualizations."""
+    paths = add_config_paths(args.data_path, {})
+    with open(args.benchmark_pickle_path, "rb") as fh:
+        benchmark_data = pickle.load(fh)
+    config = next((v for v in benchmark_data["videos"] if v["video_idx"] == args.video_id), None)
+    orig_h, orig_w = config["h"], config["w"]
+    frames = torch.from_numpy(_load_video_u8(paths["video_folder"], None)).to(device)
+    pred_h, pred_w = args.infer_res_size
+    out_dir = paths["model_vis_dir"]
+    os.makedirs(out_dir, exist_ok=True)
+    written = []
+    for idx, frame_idx in enumerate(sorted(config["target_points"].keys())):
+        if idx > 0 and args.only_first_frame:
+            break
+        gt = np.array(config["target_points"][frame_idx])
+        gt_occ = np.array(config["occluded"][frame_idx])
+        pred = np.load(os.path.join(paths["trajectories_dir"], f"trajectories_{frame_idx}.npy"))
+        pred = pred * np.array([orig_w / pred_w, orig_h / pred_h], dtype=np.float32)   # to the video's resolution
+        if args.use_gt_occ:
+            pred_occ = gt_occ
+        else:
+            occ_file = os.path.join(paths["occlusions_dir"], f"occlusion_preds_{frame_idx}.npy")
+            assert os.path.exists(occ_file), f"occlusion_preds_{frame_idx}.npy does not exist"
+            pred_occ = np.load(occ_file)
+        video = visualize_trajectories_with_gt(frames, pred, gt, pred_occ, gt_occ, badja_vis_type=args.badja_vis_type)
+        written.append(save_video(video, os.path.join(out_dir, f"pred_vs_gt_frame_idx_{frame_idx}_fps_{args.fps}.mp4"), fps=args.fps))
+    print("Saved to", out_dir)
+    return written
+
+
+def make_pred_vs_gt_parser() -> argparse.ArgumentParser:
+    """visualize_pred_vs_gt.py:109-118, argument for argument."""
+    p = argparse.ArgumentParser(prog="python -m dino_tracker_amd.visualize pred-vs-gt",
+                                description="prediction-against-ground-truth videos of a benchmark video")
+    p.add_argument("--data-path", default="./dataset/libby", type=str, required=True)
+    p.add_argument("--benchmark-pickle-path", type=str, required=True, help="the benchmark file; it is unpickled")
+    p.add_argument("--video-id", type=int, required=True)
+    p.add_argument("--infer-res-size", type=int, nargs=2, default=(476, 854), help="inference resolution (h, w), as in train.yaml")
+    p.add_argument("--badja-vis-type", action="store_true", help="render only the frames with ground-truth annotations (BADJA)")
+    p.add_argument("--only-first-frame", action="store_true", help="only the query points of the first start frame")
+    p.add_argument("--use-gt-occ", action="store_true", help="use the ground-truth occlusion for the predictions too")
+    p.add_argument("--fps", type=int, default=10, help="fps=10 for TAP-Vid, fps=2 for BADJA")
+    return p
+
+
 def make_parser() -> argparse.ArgumentParser:
     """visualize_rainbow.py:145-158, argument for argument."""
     p = argparse.ArgumentParser(description=__doc__.split("\n")[0])
@@ -433,5 +593,13 @@ def make_parser() -> argparse.ArgumentParser:
     return p
 
 
+def main(argv=None):
+    """`pred-vs-gt` as the first argument selects save_prediction_vs_gt; everything else is the track-video command line."""
+    argv = sys.argv[1:] if argv is None else list(argv)
+    if argv[:1] == ["pred-vs-gt"]:
+        return save_prediction_vs_gt(make_pred_vs_gt_parser().parse_args(argv[1:]))
+    return run(make_parser().parse_args(argv))
+
+
 if __name__ == "__main__":
-    run(make_parser().parse_args())
+    main()

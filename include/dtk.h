@@ -488,6 +488,19 @@ int dtk_tapvid_counts(const float* pred_tracks, const uint8_t* pred_occluded, co
                       float gt_scale_x, float gt_scale_y, int first_mode, int N, int T, unsigned long long* counts18,
                       void* stream);
 
+/* ---- BADJA metric counts (eval/metrics.py:226-287, compute_badja_metrics_for_video for one video) ------------------
+ * pred_tracks [N][T][2] f32 (x, y), scaled in float32 by the two factors first (metrics.py:266-267); gt_tracks [N][T][2]
+ * f64, as the benchmark pickle holds them; gt_occluded [N][T] uint8 (0 = visible); segmentations [T_seg][H][W], uint8
+ * (seg_is_float = 0) or f32 (1), 1 <= T_seg <= T.  area[t] = number of pixels > 0 (integer reduction into `areas`
+ * [T_seg] uint64, device, overwritten); thr[t] = float32(0.2) sqrtf(float32(area[t])).  For every point and every t in
+ * 1 .. T_seg - 1 that is visible: dist = sqrt((px - gx)^2 + (py - gy)^2) in float64 without FMA contraction.
+ * counts3 (device, uint64): [0] visible, [1] dist < thr[t], [2] dist < 3.0.  H W >= 2^24 is refused (the reference's
+ * float32 sum stops being the pixel count there).  Integer atomics only: two calls give the same bits.  The host folds
+ * the counts into acc_seg / acc_3px (dino_tracker_amd/tapvid.py). */
+int dtk_badja_counts(const float* pred_tracks, const double* gt_tracks, const uint8_t* gt_occluded, const void* segmentations,
+                     int32_t seg_is_float, float pred_scale_x, float pred_scale_y, int32_t N, int32_t T, int32_t T_seg,
+                     int32_t H, int32_t W, unsigned long long* areas, unsigned long long* counts3, void* stream);
+
 /* ---- per-video test-time training: train-mode BatchNorm2d of the Delta-DINO CNN ------------------------
  * Replaces nn.BatchNorm2d in training mode inside DeltaDINO.forward (models/networks/delta_dino.py:38,53-55; batches of
  * <= 8 frames, models/tracker.py:118-124) and its autograd backward.  x, y, dy, dx: [N][C][HW] float32 (NCHW).
@@ -669,9 +682,10 @@ int dtk_flow_traj_emit(int32_t T, int32_t h, int32_t w, int32_t s, int32_t min_t
  * tiled, ordered alpha-blending rasteriser.  The picture is DEFINED in docs/RENDER.md (pixel centres, analytic one-pixel coverage
  * ramps, c <- c (1 - a cov) + colour a cov in fp32, draw order = the reference's); it is not matplotlib's Agg output. -----------
  * A primitive RECORD is DTK_RENDER_RECORD_WORDS = 12 32-bit words:
- *   [0] kind (int32: DTK_RENDER_SEGMENT / _DISC / _DIAMOND)   [1..4] x0 y0 x1 y1 (markers: both ends the centre)
- *   [5] size: half-width (segment), radius (disc), L1 radius rho (diamond)       [6..8] r g b in [0, 1]      [9] a
- *   [10] 1 / |p1 - p0|^2 (0 for a zero-length segment and for markers)           [11] frame in the group (int32)
+ *   [0] kind (int32: DTK_RENDER_SEGMENT / _DISC / _DIAMOND / _RING)   [1..4] x0 y0 x1 y1 (markers: both ends the centre)
+ *   [5] size: half-width (segment), radius (disc, ring), L1 radius rho (diamond)  [6..8] r g b in [0, 1]      [9] a
+ *   [10] 1 / |p1 - p0|^2 (0 for a zero-length segment and for markers; RING: the half stroke width hw)
+ *   [11] frame in the group (int32)
  * Records are stored in draw order: frame by frame, and within a frame in the order the reference draws.
  *
  * dtk_render_prims writes the records of frames f0 .. f0 + F - 1 of a video of T frames with N points.  points [N][T][2] fp32,
@@ -680,8 +694,14 @@ int dtk_flow_traj_emit(int32_t T, int32_t h, int32_t w, int32_t s, int32_t min_t
  *   only j < i is read); frame i has N (i + 1) records: the markers, then for j = i - 1 .. 0 the N segments P(n, j) -> P(n, j + 1)
  *   with the reference's out-of-frame rule, clamping and fade (docs/RENDER.md).  A record with a = 0 bins nowhere.
  *   dtk_render_prim_count(mode, N, f0, F) is the number of records of the group.
+ * dtk_render_pred_gt_prims (visualization/visualize_pred_vs_gt.py:13-38): pred_xy / gt_xy [N][T][2] int32 (already truncated
+ *   by the caller), pred_occluded / gt_occluded [N][T] uint8, colors [N][3] fp32 -> exactly 2 records per (frame, point), frame
+ *   by frame, ascending n: both visible: red (1, 0, 0) segment pred -> gt of half width thickness / 2, disc of `radius` in the
+ *   point's colour; gt occluded only: the two diagonals (x -+ cross_size, y -+ cross_size) of half width thickness / 2 in the
+ *   point's colour; pred occluded only: red segment of half width (thickness / 2 as integers) / 2, ring of `radius` with hw = 1;
+ *   both occluded: two all-zero records (a = 0).  Every drawn record has a = 1.
  * dtk_render_tile_counts: counts[p] = number of DTK_RENDER_TILE x DTK_RENDER_TILE tiles the bounding box of record p meets: the
- *   extent grown by size + 0.5 (diamond: size + sqrt(1/2)), clipped to the W x H frame; 0 when a <= 0, a coordinate is not finite or the record's frame is not in 0 .. F - 1.
+ *   extent grown by size + 0.5 (diamond: size + sqrt(1/2); ring: size + hw + 0.5), clipped to the W x H frame; 0 when a <= 0, a coordinate is not finite or the record's frame is not in 0 .. F - 1.
  * dtk_render_tile_keys: offsets[p] = exclusive prefix sum of counts (int64); writes one key per (tile, record):
  *   key = ((frame * tiles_y + ty) * tiles_x + tx) << 32 | p.  Keys are unique, so their sorted order does not depend on which
  *   thread wrote which; ascending order inside one (frame, tile) is draw order.
@@ -694,6 +714,7 @@ int dtk_flow_traj_emit(int32_t T, int32_t h, int32_t w, int32_t s, int32_t min_t
 #define DTK_RENDER_SEGMENT 0
 #define DTK_RENDER_DISC 1
 #define DTK_RENDER_DIAMOND 2
+#define DTK_RENDER_RING 3 /* stroked circle: coverage clamp(0.5 + hw - |d - r|, 0, 1) */
 #define DTK_RENDER_DOTTED 0
 #define DTK_RENDER_TAILS 1
 #define DTK_RENDER_RECORD_WORDS 12
@@ -704,6 +725,9 @@ size_t dtk_render_group_bytes(int64_t prims, int64_t keys, int32_t F, int32_t H,
 int dtk_render_prims(const float* points, const uint8_t* occluded, const float* maps, const float* colors, int32_t N, int32_t T,
                      int32_t f0, int32_t F, int32_t H, int32_t W, int32_t mode, int32_t marker_kind, float marker_size,
                      float half_width, int32_t trail_fade, float* records, void* stream);
+int dtk_render_pred_gt_prims(const int32_t* pred_xy, const int32_t* gt_xy, const uint8_t* pred_occluded,
+                             const uint8_t* gt_occluded, const float* colors, int32_t N, int32_t T, int32_t f0, int32_t F,
+                             int32_t thickness, int32_t radius, int32_t cross_size, float* records, void* stream);
 int dtk_render_tile_counts(const float* records, int64_t P, int32_t F, int32_t H, int32_t W, int32_t* counts, void* stream);
 int dtk_render_tile_keys(const float* records, const int64_t* offsets, int64_t P, int32_t F, int32_t H, int32_t W, int64_t K,
                          int64_t* keys, void* stream);
