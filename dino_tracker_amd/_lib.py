@@ -220,6 +220,9 @@ SIGNATURES = {
     "dtk_render_tile_keys": (c_int, [c_void_p, c_void_p, ctypes.c_int64, c_int, c_int, c_int, ctypes.c_int64, c_void_p, c_void_p]),
     "dtk_render_blend": (c_int, [c_void_p, c_void_p, ctypes.c_int64, c_void_p, ctypes.c_int64, c_void_p, c_int, c_int, c_int,
                                  c_void_p, c_void_p, c_void_p]),
+    "dtk_resize_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "dtk_resize_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int,
+                              c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
 _LIB = None

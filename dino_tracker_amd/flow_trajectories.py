@@ -167,7 +167,7 @@ def run(frames_path: Optional[str], output_path: str, infer_res_size=None, thres
         if frames_path is None:
             raise ValueError("--frames-path or --flows-path is required")
         from .train import load_video
-        video = load_video(frames_path, resize=tuple(infer_res_size) if infer_res_size is not None else None)
+        video = load_video(frames_path, resize=tuple(infer_res_size) if infer_res_size is not None else None, device=device)
         traj = extract_trajectories(video, torchvision_raft(device), threshold, min_trajectory_length, filter_using_direct_flow,
                                     direct_flow_threshold, device)
     traj = traj.cpu()

@@ -183,7 +183,7 @@ def run_masks(config_path: str, data_path: str, device="cuda:0", from_video: boo
     emb_path = config["mask_dino_embed_video_path"]
     if from_video and not os.path.exists(emb_path):
         from .train import load_video
-        video = load_video(_need(config["video_folder"], "video frames"), resize=(h, w))
+        video = load_video(_need(config["video_folder"], "video frames"), resize=(h, w), device=device)
         _, details = fg_mask.fg_masks_from_video(video, config["mask_dino_model_name"], config["mask_dino_layer"],
                                                  config["mask_dino_stride"], img_size=(h, w), device=device,
                                                  fg_mask_threshold=thr, return_details=True)

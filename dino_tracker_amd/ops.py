@@ -759,3 +759,42 @@ def render_records(frames: torch.Tensor, records: torch.Tensor, want_float: bool
         stats["keys"] = stats.get("keys", 0) + K
         stats["groups"] = stats.get("groups", 0) + 1
     return render_blend(frames, records, sorted_keys, render_tile_starts(sorted_keys, F, H, W), want_float)
+
+
+# ---- video ingest (csrc/resize.hip): Pillow's 8-bit separable resampler; the tables are video_io.lanczos_tables' ----------------
+RESIZE_OUT_U8_HWC, RESIZE_OUT_F32_CHW = 0, 1
+RESIZE_FORCE_GENERAL = 1
+RESIZE_TILE_H, RESIZE_TILE_W = 32, 64
+
+
+def resize_workspace_bytes(N: int, H: int, W: int, C: int, h: int, w: int, ksize_y: int, options: int = 0) -> int:
+    """dtk_resize_workspace_bytes: bytes of the uint8 intermediate the general form needs (0: fused form, or a pass is skipped)."""
+    return int(lib().dtk_resize_workspace_bytes(int(N), int(H), int(W), int(C), int(h), int(w), int(ksize_y), int(options)))
+
+
+def resize_u8(frames: torch.Tensor, h: int, w: int, kx: Optional[torch.Tensor], bx: Optional[torch.Tensor],
+              ky: Optional[torch.Tensor], by: Optional[torch.Tensor], u8_to_f32: Optional[torch.Tensor],
+              out_form: int = RESIZE_OUT_U8_HWC, options: int = 0) -> torch.Tensor:
+    """dtk_resize_u8: frames [N, H, W, C] uint8 -> uint8 [N, h, w, C] or fp32 [N, C, h, w].  k? int32 [out, ksize] weights and
+    b? int32 [out, 2] bounds per axis (None for an axis whose size does not change), u8_to_f32 fp32 [256] for the fp32 form."""
+    if frames.dim() != 4 or frames.numel() == 0:
+        raise RuntimeError(f"dino_tracker_amd: frames must be [N, H, W, C] uint8, got {tuple(frames.shape)}")
+    N, H, W, C = (int(v) for v in frames.shape)
+    for k, b, n_out, axis in ((kx, bx, w, "x"), (ky, by, h, "y")):
+        if k is not None and (k.dim() != 2 or k.shape[0] != n_out or b is None or tuple(b.shape) != (n_out, 2)):
+            raise RuntimeError(f"dino_tracker_amd: the {axis} tables must be [{n_out}, ksize] and [{n_out}, 2], got "
+                               f"{tuple(k.shape)} and {None if b is None else tuple(b.shape)}")
+    if u8_to_f32 is not None and u8_to_f32.numel() != 256:
+        raise RuntimeError(f"dino_tracker_amd: u8_to_f32 must hold 256 values, got {u8_to_f32.numel()}")
+    ksx = int(kx.shape[1]) if kx is not None else 0
+    ksy = int(ky.shape[1]) if ky is not None else 0
+    if out_form == RESIZE_OUT_F32_CHW:
+        out = torch.empty((N, C, int(h), int(w)), dtype=torch.float32, device=frames.device)
+    else:
+        out = torch.empty((N, int(h), int(w), C), dtype=torch.uint8, device=frames.device)
+    nbytes = resize_workspace_bytes(N, H, W, C, h, w, ksy, options) if ky is not None else 0
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=frames.device) if nbytes else None
+    check(lib().dtk_resize_u8(_p(frames, torch.uint8), N, H, W, C, int(h), int(w), _p(kx, torch.int32), _p(bx, torch.int32), ksx,
+                              _p(ky, torch.int32), _p(by, torch.int32), ksy, _p(u8_to_f32, torch.float32), int(out_form),
+                              int(options), _p(out), _p(ws), nbytes, _stream()))
+    return out

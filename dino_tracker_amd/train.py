@@ -39,8 +39,12 @@ def load_masks(masks_path, h_resize=476, w_resize=854) -> torch.Tensor:
     return torch.nn.functional.interpolate(masks, size=(h_resize, w_resize), mode="nearest")[:, 0]
 
 
-def load_video(video_folder, resize=None) -> torch.Tensor:
-    """data/data_utils.py:79-104: frames in file order, LANCZOS-resized to `resize` = (h, w), ToTensor (HWC uint8 -> CHW / 255)."""
+def load_video(video_folder, resize=None, device=None) -> torch.Tensor:
+    """data/data_utils.py:79-104: frames in file order, LANCZOS-resized to `resize` = (h, w), ToTensor (HWC uint8 -> CHW / 255).
+    With a CUDA `device` the frames are uploaded as uint8 and resized there (video_io.load_video): the same bits, on the device."""
+    if device is not None and torch.device(device).type == "cuda":
+        from .video_io import load_video as device_load_video
+        return device_load_video(video_folder, resize=resize, device=device)
     from PIL import Image
     files = sorted(list(Path(video_folder).glob("*.jpg")) + list(Path(video_folder).glob("*.png")))
     frames = []
@@ -92,7 +96,7 @@ class StandaloneBase:
     def get_model(self):
         from .tracker import Tracker
         cfg = self.config
-        video = load_video(self.video_path, resize=(cfg["video_resh"], cfg["video_resw"])).to(self.device)
+        video = load_video(self.video_path, resize=(cfg["video_resh"], cfg["video_resw"]), device=self.device).to(self.device)
         model = Tracker(video=video, device=self.device, dino_embed_path=self.dino_embed_path, dino_patch_size=cfg["dino_patch_size"],
                         stride=cfg["stride"], ckpt_path=self.ckpt_folder, cyc_n_frames=cfg["cyc_n_frames"],
                         cyc_batch_size_per_frame=cfg["cyc_batch_size_per_frame"], cyc_fg_points_ratio=cfg["cyc_fg_points_ratio"],

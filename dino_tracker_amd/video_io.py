@@ -1,0 +1,173 @@
+"""Video ingest on the device: frames are decoded by Pillow on the host, uploaded once as uint8, and LANCZOS-resized by libdtk
+(csrc/resize.hip) with Pillow's own 8-bit arithmetic, so the result is bit-equal to `Image.resize(..., Image.LANCZOS)` followed by
+`ToTensor` -- what data/data_utils.py:79-104 (`load_video`) and :47-52 (`resize_tensor_frames_lanczos`) compute on the CPU.
+
+Pillow's resampler (src/libImaging/Resample.c) is two separable passes of integer arithmetic on uint8 with a uint8 intermediate,
+horizontal first.  The filter itself is evaluated HERE, on the host, in Python floats (C doubles, libm's sin, as Pillow does) into
+22-bit fixed-point tables; the kernels only multiply and add, so they are exact whatever the device's float unit does."""
+from __future__ import annotations
+
+import functools
+import math
+from pathlib import Path
+from typing import Dict, Optional, Tuple
+
+import numpy as np
+import torch
+
+from . import ops
+
+PRECISION_BITS = 22   # Resample.c: 32 - 8 - 2
+LANCZOS_SUPPORT = 3.0
+
+
+def _lanczos(x: float) -> float:
+    """Resample.c lanczos_filter / sinc_filter."""
+    if not -3.0 <= x < 3.0:
+        return 0.0
+
+    def sinc(v: float) -> float:
+        if v == 0.0:
+            return 1.0
+        v = v * math.pi
+        return math.sin(v) / v
+    return sinc(x) * sinc(x / 3)
+
+
+@functools.lru_cache(maxsize=64)
+def lanczos_tables(in_size: int, out_size: int) -> Tuple[np.ndarray, np.ndarray]:
+    """Resample.c precompute_coeffs + normalize_coeffs_8bpc for the whole axis (box = (0, in_size)): int32 weights [out, ksize]
+    (zero beyond a row's count) and int32 bounds [out, 2] = (first input index, count).  Read-only arrays, cached per size pair."""
+    in_size, out_size = int(in_size), int(out_size)
+    if in_size < 1 or out_size < 1:
+        raise ValueError(f"lanczos_tables: sizes must be positive, got {in_size} -> {out_size}")
+    scale = in_size / out_size
+    filterscale = max(scale, 1.0)
+    support = LANCZOS_SUPPORT * filterscale
+    ksize = int(math.ceil(support)) * 2 + 1
+    ss = 1.0 / filterscale
+    k = np.zeros((out_size, ksize), dtype=np.int64)
+    b = np.zeros((out_size, 2), dtype=np.int32)
+    one = float(1 << PRECISION_BITS)
+    for i in range(out_size):
+        center = (i + 0.5) * scale
+        xmin = max(int(center - support + 0.5), 0)
+        xmax = min(int(center + support + 0.5), in_size) - xmin
+        ws = [_lanczos((j + xmin - center + 0.5) * ss) for j in range(xmax)]
+        ww = 0.0
+        for v in ws:
+            ww += v
+        if ww != 0.0:
+            ws = [v / ww for v in ws]
+        k[i, :xmax] = [int(v * one - 0.5) if v < 0 else int(v * one + 0.5) for v in ws]
+        b[i] = (xmin, xmax)
+    # what the kernels rely on: 24-bit multiplies are exact, and no row can overflow the int32 accumulator
+    assert int(np.abs(k).max()) < (1 << 23), (in_size, out_size)
+    assert int(255 * np.abs(k).sum(axis=1).max()) + (1 << 21) < (1 << 31), (in_size, out_size)
+    k = k.astype(np.int32)
+    k.setflags(write=False)
+    b.setflags(write=False)
+    return k, b
+
+
+_DEVICE_TABLES: Dict[tuple, Tuple[torch.Tensor, torch.Tensor]] = {}
+_DEVICE_LUT: Dict[torch.device, torch.Tensor] = {}
+
+
+def _device_tables(in_size: int, out_size: int, device: torch.device) -> Tuple[torch.Tensor, torch.Tensor]:
+    key = (in_size, out_size, device)
+    if key not in _DEVICE_TABLES:
+        k, b = lanczos_tables(in_size, out_size)
+        _DEVICE_TABLES[key] = (torch.from_numpy(k.copy()).to(device), torch.from_numpy(b.copy()).to(device))
+    return _DEVICE_TABLES[key]
+
+
+def _u8_to_f32(device: torch.device) -> torch.Tensor:
+    """ToTensor's u8 / 255 for every byte, rounded by the HOST: the fp32 output is a table look-up."""
+    if device not in _DEVICE_LUT:
+        _DEVICE_LUT[device] = torch.arange(256, dtype=torch.uint8).float().div(255).to(device)
+    return _DEVICE_LUT[device]
+
+
+def resize_lanczos(frames_u8: torch.Tensor, h: int, w: int, out: str = "u8", force_general: bool = False) -> torch.Tensor:
+    """Image.resize((w, h), Image.LANCZOS) of device uint8 frames [N, H, W, C] or [H, W, C] (C = 1 or 3).
+    out="u8": uint8 [N, h, w, C];  out="f32": float32 [N, C, h, w] = ToTensor (u8 / 255).  `force_general` takes the two-launch
+    form of the kernel where the fused one would run (tests)."""
+    if out not in ("u8", "f32"):
+        raise ValueError(f"resize_lanczos: out must be 'u8' or 'f32', got {out!r}")
+    if not frames_u8.is_cuda:
+        raise RuntimeError("dino_tracker_amd: tensor is not on a GPU -- the hot path has no CPU fallback")
+    single = frames_u8.dim() == 3
+    x = frames_u8[None] if single else frames_u8
+    if x.dim() != 4 or x.dtype != torch.uint8 or x.shape[-1] not in (1, 3) or x.numel() == 0:
+        raise RuntimeError(f"dino_tracker_amd: frames must be [N, H, W, C] or [H, W, C] uint8 with C in (1, 3), got "
+                           f"{tuple(frames_u8.shape)} {frames_u8.dtype}")
+    h, w = int(h), int(w)
+    if h < 1 or w < 1:
+        raise ValueError(f"resize_lanczos: the output size must be positive, got {h} x {w}")
+    H, W = int(x.shape[1]), int(x.shape[2])
+    dev = x.device
+    kx, bx = _device_tables(W, w, dev) if W != w else (None, None)
+    ky, by = _device_tables(H, h, dev) if H != h else (None, None)
+    y = ops.resize_u8(x.contiguous(), h, w, kx, bx, ky, by, _u8_to_f32(dev) if out == "f32" else None,
+                      ops.RESIZE_OUT_F32_CHW if out == "f32" else ops.RESIZE_OUT_U8_HWC,
+                      ops.RESIZE_FORCE_GENERAL if force_general else 0)
+    return y[0] if single else y
+
+
+def resize_tensor_frames_lanczos(frames: torch.Tensor, h: int, w: int) -> torch.Tensor:
+    """data/data_utils.py:47-52 on the device: float frames [T, C, H, W] -> ToPILImage (mul(255) in fp32, truncated to uint8 --
+    so v / 255 * 255 may land one below v, as there) -> LANCZOS resize -> ToTensor.  The quantisation and the change of layout
+    are torch on the device; the resize is libdtk's."""
+    if not frames.is_cuda:
+        raise RuntimeError("dino_tracker_amd: tensor is not on a GPU -- the hot path has no CPU fallback")
+    if frames.dim() != 4 or not frames.is_floating_point() or frames.shape[1] not in (1, 3):
+        raise RuntimeError(f"dino_tracker_amd: frames must be float [T, C, H, W] with C in (1, 3), got {tuple(frames.shape)} "
+                           f"{frames.dtype}")
+    u8 = frames.float().mul(255).to(torch.uint8).permute(0, 2, 3, 1).contiguous()
+    return resize_lanczos(u8, h, w, out="f32")
+
+
+def video_files(video_folder) -> list:
+    """data/data_utils.py:91-92: *.jpg then *.png, sorted together."""
+    path = Path(video_folder)
+    return sorted(list(path.glob("*.jpg")) + list(path.glob("*.png")))
+
+
+def _decode_pinned(files) -> Optional[torch.Tensor]:
+    """All frames into ONE pinned uint8 [T, H, W, C] buffer; None when they are not all RGB or all L of one size."""
+    from PIL import Image
+    buf = view = None
+    first = None
+    for t, f in enumerate(files):
+        with Image.open(str(f)) as img:
+            if img.mode not in ("RGB", "L") or (first is not None and (img.mode, img.size) != first):
+                return None
+            if first is None:
+                first = (img.mode, img.size)
+                buf = torch.empty((len(files), img.size[1], img.size[0], len(img.mode)), dtype=torch.uint8, pin_memory=True)
+                view = buf.numpy()
+            view[t] = np.asarray(img).reshape(view.shape[1:])
+    return buf
+
+
+def load_video(video_folder, resize=None, num_frames: Optional[int] = None, device="cuda:0") -> torch.Tensor:
+    """data/data_utils.py:79-104 with the resize on the device: the frames of `video_folder` in file order (the first
+    `num_frames`), decoded on the host, uploaded once as uint8, LANCZOS-resized to `resize` = (h, w) and converted as ToTensor
+    does -> float32 [T, C, h, w] on `device`, bit-equal to the host path.  Frames that are not all RGB or all L of one size take
+    the host path (train.load_video) and are uploaded afterwards."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("dino_tracker_amd: video_io.load_video needs a GPU device -- the hot path has no CPU fallback")
+    files = video_files(video_folder)
+    files = files[:num_frames] if num_frames is not None else files
+    if not files:
+        raise RuntimeError(f"dino_tracker_amd: no *.jpg / *.png frames in {video_folder}")
+    frames = _decode_pinned(files)
+    if frames is None:
+        from .train import load_video as host_load_video
+        video = host_load_video(video_folder, resize=resize)
+        return (video[:num_frames] if num_frames is not None else video).to(device)
+    frames = frames.to(device, non_blocking=True)
+    h, w = (int(resize[0]), int(resize[1])) if resize is not None else (int(frames.shape[1]), int(frames.shape[2]))
+    return resize_lanczos(frames, h, w, out="f32")

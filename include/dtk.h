@@ -734,6 +734,38 @@ int dtk_render_tile_keys(const float* records, const int64_t* offsets, int64_t P
 int dtk_render_blend(const uint8_t* frames_in, const float* records, int64_t P, const int64_t* sorted_keys, int64_t K,
                      const int64_t* tile_start, int32_t F, int32_t H, int32_t W, uint8_t* out_u8, float* out_f32, void* stream);
 
+/* ---- Video ingest: Pillow's 8-bit separable resampler (Image.resize on uint8, src/libImaging/Resample.c) on the device ---------
+ * dtk_resize_u8 resamples N frames  in [N][H][W][C] uint8 (interleaved, C = 1 or 3)  to  h x w.  out_form:
+ *   DTK_RESIZE_OUT_U8_HWC  : out [N][h][w][C] uint8
+ *   DTK_RESIZE_OUT_F32_CHW : out [N][C][h][w] fp32 = u8_to_f32[value]  (the caller's 256-entry table: ToTensor's u8 / 255 as the
+ *                            host rounds it, so the bits do not depend on the device's division)
+ * The filter lives in the caller's tables (device pointers), per axis:  k [out][ksize] int32 weights in 22-bit fixed point and
+ *   b [out][2] int32 (first input index, count <= ksize); rows of k beyond `count` are not read.  The kernels never evaluate a
+ *   filter.  Arithmetic, per pass:  acc = 2^21 + sum_j in[first + j] * k[j]  in int32,  out = clamp(acc >> 22, 0, 255)  (arithmetic
+ *   shift); horizontal pass first, vertical pass on its uint8 result.  The products are formed by 24-bit multiplies: |k| < 2^23,
+ *   and the caller guarantees 255 * sum|k| + 2^21 < 2^31 per row.  A pass whose sizes are equal (W == w, H == h) is skipped and
+ *   its tables are not read (they may be null).  Bounds are clamped to the frame before use: a bad table gives wrong pixels, never
+ *   an access outside the buffers.
+ * Two forms.  FUSED: one workgroup per DTK_RESIZE_TILE_H x DTK_RESIZE_TILE_W output tile runs the horizontal pass for the input
+ *   rows the tile needs into LDS (uint8), the vertical pass from LDS, and writes the output in its final form; the input is read
+ *   once (plus the rows neighbouring tiles share), nothing else touches memory.  It is taken when the rows of one tile,
+ *   min(H, (TILE_H - 1) * H / h + ksize_y + 1) of them (TILE_H when the vertical pass is skipped), fit in 64 KiB of LDS at
+ *   TILE_W * C bytes each -- the caller's vertical bounds must stay inside that span, as those of any resampling filter of
+ *   support (ksize_y - 1) / 2 do.  GENERAL: one launch per pass with the uint8 intermediate [N][H][w][C] in `workspace`
+ *   (dtk_resize_workspace_bytes; 0 when the fused form is taken or a pass is skipped).  DTK_RESIZE_FORCE_GENERAL in `options`
+ *   selects the general form regardless. */
+#define DTK_RESIZE_OUT_U8_HWC 0
+#define DTK_RESIZE_OUT_F32_CHW 1
+#define DTK_RESIZE_FORCE_GENERAL 1
+#define DTK_RESIZE_TILE_H 32
+#define DTK_RESIZE_TILE_W 64
+size_t dtk_resize_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t C, int32_t h, int32_t w, int32_t ksize_y,
+                                  int32_t options);
+int dtk_resize_u8(const uint8_t* in, int32_t N, int32_t H, int32_t W, int32_t C, int32_t h, int32_t w, const int32_t* kx,
+                  const int32_t* bx, int32_t ksize_x, const int32_t* ky, const int32_t* by, int32_t ksize_y,
+                  const float* u8_to_f32, int32_t out_form, int32_t options, void* out, void* workspace, size_t workspace_bytes,
+                  void* stream);
+
 #ifdef __cplusplus
 }
 #endif
