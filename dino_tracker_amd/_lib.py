@@ -174,6 +174,10 @@ SIGNATURES = {
                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "dtk_occlusion": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_void_p, c_int,
                               c_int, c_void_p]),
+    "dtk_build_anchor_sources_needed": (c_int, [c_void_p, c_float, c_float, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dtk_occlusion_needed": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_void_p, c_int,
+                                     c_int, c_void_p]),
     "dtk_tapvid_counts": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float,
                                   c_int, c_int, c_int, c_void_p, c_void_p]),
     "dtk_badja_counts": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float, c_float, c_int, c_int, c_int, c_int, c_int,

@@ -4,12 +4,70 @@
 //                              reference's dict n -> [A_n, T, 2]); source list of the anchor stage sorted by
 //                              anchor frame so that consecutive sources share their target feature frame.
 //   dtk_occlusion            : d[k][t] = |G[k][t] - traj[a_k]|, lower median over anchors, threshold tau.
+//   dtk_build_anchor_sources_needed / dtk_occlusion_needed : the same pairs and the same flags from the anchor maps the
+//                              flags depend on.  occ = (med > tau) | low with tau = max of med over the anchor frames, so an
+//                              anchor frame has med <= tau (occ = low) and a low frame is occluded whatever its median: only
+//                              the UNDECIDED frames (neither anchor nor low) need a median, and they need tau, i.e. the
+//                              anchor frames.  A query with no undecided frame (or no anchor) needs no anchor map at all.
 #include "common.h"
 
 namespace {
 
 __device__ __forceinline__ bool is_anchor(const float* cs, float th, int n, int T, int t) {
     return cs[(size_t)n * T + t] >= th;
+}
+
+// the frames of query n whose column of the anchor maps the flags can depend on: anchors (they set tau) and undecided frames
+// (cs neither >= anchor_th nor < cos_th; a NaN cs is undecided).  The rest -- low and not an anchor -- is occluded by cs alone.
+__device__ __forceinline__ bool is_undecided(float c, float anchor_th, float cos_th) { return !(c >= anchor_th) && !(c < cos_th); }
+__device__ __forceinline__ bool is_needed(float c, float anchor_th, float cos_th) { return c >= anchor_th || !(c < cos_th); }
+
+// n_anchors[n] as anchor_count_kernel; need_w[n] = needed columns of query n if it is OPEN (>= 1 anchor and >= 1 undecided
+// frame), else 0: the sources every pair of the query emits
+__global__ __launch_bounds__(256) void query_need_kernel(const float* __restrict__ cs, float anchor_th, float cos_th, int N, int T,
+                                                         int32_t* __restrict__ n_anchors, int32_t* __restrict__ need_w) {
+    const int n = blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= N) return;
+    int anchors = 0, undecided = 0, needed = 0;
+    for (int t = 0; t < T; ++t) {
+        const float c = cs[(size_t)n * T + t];
+        anchors += c >= anchor_th ? 1 : 0;
+        undecided += is_undecided(c, anchor_th, cos_th) ? 1 : 0;
+        needed += is_needed(c, anchor_th, cos_th) ? 1 : 0;
+    }
+    n_anchors[n] = anchors;
+    need_w[n] = (anchors > 0 && undecided > 0) ? needed : 0;
+}
+
+// frame_cnt[a] = sources of anchor frame a = sum of need_w[n] over the queries with anchor (n, a)
+__global__ __launch_bounds__(256) void frame_weight_kernel(const float* __restrict__ cs, float th, int N, int T,
+                                                           const int32_t* __restrict__ need_w, int32_t* __restrict__ frame_cnt) {
+    __shared__ int red[4];
+    const int a = blockIdx.x;
+    int c = 0;
+    for (int n = threadIdx.x; n < N; n += 256) c += is_anchor(cs, th, n, T, a) ? need_w[n] : 0;
+    c = wave_sum_i(c);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) frame_cnt[a] = red[0] + red[1] + red[2] + red[3];
+}
+
+// one block: counts[0] = pairs, counts[1] = emitted sources, counts[3] = open queries
+__global__ __launch_bounds__(256) void finalize_needed_counts_kernel(const int32_t* __restrict__ pair_off,
+                                                                     const int32_t* __restrict__ frame_off,
+                                                                     const int32_t* __restrict__ need_w, int N, int T,
+                                                                     int32_t* __restrict__ counts) {
+    __shared__ int red[4];
+    int open = 0;
+    for (int n = threadIdx.x; n < N; n += 256) open += need_w[n] > 0 ? 1 : 0;
+    open = wave_sum_i(open);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = open;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        counts[0] = pair_off[N];
+        counts[1] = frame_off[T];
+        counts[3] = red[0] + red[1] + red[2] + red[3];
+    }
 }
 
 __global__ __launch_bounds__(256) void anchor_count_kernel(const float* __restrict__ cs, float th, int N, int T,
@@ -114,6 +172,44 @@ __global__ __launch_bounds__(256) void emit_sources_kernel(const float* __restri
     }
 }
 
+// block a as emit_sources_kernel, but pair (n, a) emits need_w[n] sources -- the needed columns of n in frame order, none for a
+// closed query -- so the position of a pair is the scan of those weights; pair_frame is written for EVERY pair
+__global__ __launch_bounds__(256) void emit_needed_sources_kernel(const float* __restrict__ cs, float anchor_th, float cos_th,
+                                                                  int N, int T, const int32_t* __restrict__ pair_off,
+                                                                  const int32_t* __restrict__ frame_off,
+                                                                  const int32_t* __restrict__ need_w,
+                                                                  int32_t* __restrict__ pair_frame,
+                                                                  int32_t* __restrict__ src_row, int32_t* __restrict__ tgt,
+                                                                  int32_t* __restrict__ out_idx) {
+    __shared__ int lds4[4];
+    const int a = blockIdx.x;
+    int carry = frame_off[a];
+    for (int n0 = 0; n0 < N; n0 += 256) {
+        const int n = n0 + threadIdx.x;
+        const bool anchor = n < N && is_anchor(cs, anchor_th, n, T, a);
+        const int weight = anchor ? need_w[n] : 0;
+        int total;
+        const int incl = block_scan_incl(weight, lds4, &total);
+        if (anchor) {
+            int rank = 0;
+            for (int t = 0; t < a; ++t) rank += is_anchor(cs, anchor_th, n, T, t) ? 1 : 0;
+            const int p = pair_off[n] + rank;
+            pair_frame[p] = a;
+            if (weight > 0) {
+                int m = carry + incl - weight;  // first source of this pair among the sources sorted by anchor frame
+                for (int t = 0; t < T; ++t) {
+                    if (!is_needed(cs[(size_t)n * T + t], anchor_th, cos_th)) continue;
+                    src_row[m] = n * T + t;
+                    tgt[m] = a;
+                    out_idx[m] = p * T + t;
+                    ++m;
+                }
+            }
+        }
+        carry += total;
+    }
+}
+
 // |G[p][t] - traj[a]| without fma contraction (the reference evaluates sqrt(dx*dx + dy*dy) with separate roundings)
 __device__ __forceinline__ float anchor_dist(const float* __restrict__ green, const float* __restrict__ tr, int p, int a,
                                              int T, int t) {
@@ -125,6 +221,9 @@ __device__ __forceinline__ float anchor_dist(const float* __restrict__ green, co
 // one block per query, one wave per frame t at a time: every anchor distance is computed ONCE into LDS (so the rank
 // selection compares stored values: an element can never compare "less than itself"), then lane k ranks d[k] against
 // all A values; the lane whose rank is the lower median's publishes it (torch.median semantics, ties by index).
+// PRUNED (dtk_occlusion_needed): green holds only what dtk_build_anchor_sources_needed listed.  A closed query gets
+// occ = low without a read of green; an open one skips the columns that are not needed (med[t] stays unwritten and unread).
+template <bool PRUNED>
 __global__ __launch_bounds__(256) void occlusion_kernel(const float* __restrict__ green,
                                                         const int32_t* __restrict__ pair_off,
                                                         const int32_t* __restrict__ pair_frame,
@@ -143,8 +242,18 @@ __global__ __launch_bounds__(256) void occlusion_kernel(const float* __restrict_
         for (int t = threadIdx.x; t < T; t += 256) occ[(size_t)n * T + t] = 1;
         return;
     }
+    if constexpr (PRUNED) {
+        int undecided = 0;
+        for (int t = threadIdx.x; t < T; t += 256) undecided |= is_undecided(cs[(size_t)n * T + t], anchor_th, cos_th) ? 1 : 0;
+        if (!__syncthreads_or(undecided)) {  // closed: every frame is an anchor (med <= tau) or low
+            for (int t = threadIdx.x; t < T; t += 256) occ[(size_t)n * T + t] = cs[(size_t)n * T + t] < cos_th ? 1 : 0;
+            return;
+        }
+    }
     const int want = (A - 1) / 2;  // torch.median: lower median
     for (int t = w; t < T; t += 4) {
+        if constexpr (PRUNED)
+            if (!is_needed(cs[(size_t)n * T + t], anchor_th, cos_th)) continue;  // wave-uniform
         for (int k = lane; k < A; k += WAVE) d[k] = anchor_dist(green, tr, p0 + k, pair_frame[p0 + k], T, t);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
@@ -168,8 +277,11 @@ __global__ __launch_bounds__(256) void occlusion_kernel(const float* __restrict_
     if (lane == 0) red[w] = tau;
     __syncthreads();
     tau = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    for (int t = threadIdx.x; t < T; t += 256)
-        occ[(size_t)n * T + t] = (med[t] > tau || cs[(size_t)n * T + t] < cos_th) ? 1 : 0;
+    for (int t = threadIdx.x; t < T; t += 256) {
+        const float c = cs[(size_t)n * T + t];
+        const bool far = (!PRUNED || is_needed(c, anchor_th, cos_th)) && med[t] > tau;
+        occ[(size_t)n * T + t] = (far || c < cos_th) ? 1 : 0;
+    }
 }
 
 }  // namespace
@@ -198,7 +310,39 @@ extern "C" int dtk_occlusion(const float* green, const int32_t* pair_off, const 
     DTK_REQUIRE(green && pair_off && pair_frame && traj && cs && occ && N >= 0 && T > 0, "dtk_occlusion: bad args");
     DTK_REQUIRE((size_t)5 * T * sizeof(float) <= 60 * 1024, "dtk_occlusion: T=%d too large", T);
     if (N == 0) return DTK_OK;
-    DTK_LAUNCH("occlusion", occlusion_kernel, dim3(N), dim3(256), (size_t)5 * T * sizeof(float), dtk_stream(stream), green,
+    DTK_LAUNCH("occlusion", occlusion_kernel<false>, dim3(N), dim3(256), (size_t)5 * T * sizeof(float), dtk_stream(stream), green,
+                       pair_off, pair_frame, traj, cs, anchor_th, cos_th, occ, N, T);
+    return DTK_OK;
+}
+
+extern "C" int dtk_build_anchor_sources_needed(const float* cs, float anchor_th, float cos_th, int N, int T, int32_t* n_anchors,
+                                               int32_t* pair_off, int32_t* pair_frame, int32_t* src_row, int32_t* tgt,
+                                               int32_t* out_idx, int32_t* counts, int32_t* scratch, void* stream) {
+    DTK_REQUIRE(cs && n_anchors && pair_off && pair_frame && src_row && tgt && out_idx && counts && scratch,
+                "dtk_build_anchor_sources_needed: null pointer");
+    DTK_REQUIRE(N > 0 && T > 0 && (long long)N * T * T < 2147483647LL, "dtk_build_anchor_sources_needed: N*T*T out of range");
+    hipStream_t st = dtk_stream(stream);
+    int32_t* frame_cnt = scratch;              // [T]
+    int32_t* frame_off = scratch + T;          // [T+1]
+    int32_t* need_w = scratch + 2 * T + 2;     // [N]
+    DTK_LAUNCH("query_need", query_need_kernel, dim3(dtk_cdiv(N, 256)), dim3(256), 0, st, cs, anchor_th, cos_th, N, T, n_anchors,
+               need_w);
+    DTK_LAUNCH("exclusive_scan", exclusive_scan_kernel, dim3(1), dim3(256), 0, st, n_anchors, pair_off, N, counts + 2);
+    DTK_LAUNCH("frame_weight", frame_weight_kernel, dim3(T), dim3(256), 0, st, cs, anchor_th, N, T, need_w, frame_cnt);
+    DTK_LAUNCH("exclusive_scan", exclusive_scan_kernel, dim3(1), dim3(256), 0, st, frame_cnt, frame_off, T, (int32_t*)nullptr);
+    DTK_LAUNCH("finalize_counts", finalize_needed_counts_kernel, dim3(1), dim3(256), 0, st, pair_off, frame_off, need_w, N, T,
+               counts);
+    DTK_LAUNCH("emit_sources", emit_needed_sources_kernel, dim3(T), dim3(256), 0, st, cs, anchor_th, cos_th, N, T, pair_off,
+               frame_off, need_w, pair_frame, src_row, tgt, out_idx);
+    return DTK_OK;
+}
+
+extern "C" int dtk_occlusion_needed(const float* green, const int32_t* pair_off, const int32_t* pair_frame, const float* traj,
+                                    const float* cs, float anchor_th, float cos_th, uint8_t* occ, int N, int T, void* stream) {
+    DTK_REQUIRE(green && pair_off && pair_frame && traj && cs && occ && N >= 0 && T > 0, "dtk_occlusion_needed: bad args");
+    DTK_REQUIRE((size_t)5 * T * sizeof(float) <= 60 * 1024, "dtk_occlusion_needed: T=%d too large", T);
+    if (N == 0) return DTK_OK;
+    DTK_LAUNCH("occlusion", occlusion_kernel<true>, dim3(N), dim3(256), (size_t)5 * T * sizeof(float), dtk_stream(stream), green,
                        pair_off, pair_frame, traj, cs, anchor_th, cos_th, occ, N, T);
     return DTK_OK;
 }

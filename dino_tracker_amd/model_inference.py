@@ -8,6 +8,14 @@ pipeline:
                                                                              dtk_build_anchor_sources + dtk_track
   5. occ[n,t] = (lower-median_a |G[n][a,t]-traj[n,a]| > tau_n) or cs[n,t] < th2     dtk_occlusion
 
+infer() runs steps 4-5 only on the maps the flags depend on (dtk_build_anchor_sources_needed + dtk_occlusion_needed):
+tau_n is the largest median over the anchor frames, so an anchor frame has occ = (cs < th2), a frame with cs < th2 is
+occluded whatever its median, and only the undecided frames (th2 <= cs < th, or a NaN cs) need a median -- of G[n][a,t] over
+the anchors a, against a tau_n that needs the anchor columns.  A query with no undecided frame needs no anchor map at all; the
+other queries skip the columns that are low and not anchors.  The flags are exactly those of the full stage; how many maps
+disappear depends on the input (none of a query with a frame in the band, all of one without).  compute_anchor_trajectories /
+compute_occlusion (the reference's dict API) and full_anchor_stage = True ($DTK_FULL_ANCHOR_STAGE=1: A / B) run every map.
+
 No per-query Python loop.  Host synchronisations per infer(): one read-back of the anchor counts (which also is the
 zero-anchor check: the reference raises there) plus the ones dtk_track(DTK_TRACK_MFMA) documents (one per call, for the
 sizes of its second / third tier); DTK_TRACK_EXACT adds none.
@@ -16,11 +24,13 @@ gathers (model_inference.py:45-49,138) and has no effect on results.
 """
 from __future__ import annotations
 
+import os
 from typing import Dict
 
 import torch
 
 from . import ops
+from ._lib import TrackStats
 from .dataset import RangeNormalizer
 from .tracker import Tracker
 
@@ -76,6 +86,7 @@ class ModelInference(torch.nn.Module):
         self.cosine_similarity_threshold = cosine_similarity_threshold
         self._anchor_buf = None
         self._idx_cache = {}
+        self.full_anchor_stage = os.environ.get("DTK_FULL_ANCHOR_STAGE", "0") == "1"   # infer(): every anchor map, as the dict API (A / B)
 
     # ---- index plumbing -------------------------------------------------------------------------------------
     def _first_pass_indices(self, N: int, T: int, device):
@@ -126,20 +137,27 @@ class ModelInference(torch.nn.Module):
         self._last_S = S
         return ops.traj_cos_sims(S, tq, N, T)
 
-    def _anchor_stage(self, trajectories, cos_sims, S=None):
+    def _anchor_stage(self, trajectories, cos_sims, S=None, needed_only=False):
+        """needed_only: only the sources the flags depend on (green stays uninitialised elsewhere: dtk_occlusion_needed)."""
         m = self.model
         N, T = trajectories.shape[:2]
         if S is None:
             S = self._sample_along(trajectories)
-        buf = ops.build_anchor_sources(cos_sims.contiguous(), self.anchor_cosine_similarity_threshold, self._anchor_buf)
+        if needed_only:
+            buf = ops.build_anchor_sources_needed(cos_sims.contiguous(), self.anchor_cosine_similarity_threshold,
+                                                  self.cosine_similarity_threshold, self._anchor_buf)
+        else:
+            buf = ops.build_anchor_sources(cos_sims.contiguous(), self.anchor_cosine_similarity_threshold, self._anchor_buf)
         self._anchor_buf = buf
-        # one read-back of (pairs, sources, queries without anchors): sizes the anchor launches exactly and is the
-        # zero-anchor check of infer() as well
+        # one read-back of (pairs, sources, queries without anchors, open queries -- needed_only): sizes the anchor launches
+        # exactly and is the zero-anchor check of infer() as well
         self.last_counts = buf.counts.cpu()
         n_src = int(self.last_counts[1])
         green = torch.empty((N * T, T, 2), dtype=torch.float32, device=trajectories.device)
         if n_src > 0:
             m.track_sources(m.features(), S, buf.src_row, buf.tgt, buf.out_idx, green, n_src)
+        else:
+            m.last_track_stats = TrackStats().as_dict()   # no anchor-stage dtk_track call: not the first pass's tiers
         return buf, green
 
     @torch.no_grad()
@@ -180,10 +198,11 @@ class ModelInference(torch.nn.Module):
         S = self._sample_along(trajs)
         tq = query_points[:, 2].to(trajs.device).to(torch.int32).contiguous()
         cos_sims = ops.traj_cos_sims(S, tq, N, T)
-        buf, green = self._anchor_stage(trajs, cos_sims, S)
+        needed_only = not self.full_anchor_stage
+        buf, green = self._anchor_stage(trajs, cos_sims, S, needed_only)
         traj_xy = trajs[..., :2].contiguous()
         occ = ops.occlusion(green, buf.pair_off, buf.pair_frame, traj_xy, cos_sims,
-                            self.anchor_cosine_similarity_threshold, self.cosine_similarity_threshold)
+                            self.anchor_cosine_similarity_threshold, self.cosine_similarity_threshold, needed_only)
         if int(self.last_counts[2]) > 0:
             raise RuntimeError("stack expects a non-empty TensorList")  # a query without anchors (model_inference.py:152)
         return traj_xy, occ

@@ -368,7 +368,7 @@ class AnchorSources:
         self.tgt = torch.empty(N * T * T, **i32)
         self.out_idx = torch.empty(N * T * T, **i32)
         self.counts = torch.zeros(4, **i32)
-        self.scratch = torch.empty(2 * T + 2, **i32)
+        self.scratch = torch.empty(2 * T + 2 + N, **i32)   # (the last N: dtk_build_anchor_sources_needed's per-query count)
 
 
 def build_anchor_sources(cs: torch.Tensor, anchor_th: float, buf: Optional[AnchorSources] = None) -> AnchorSources:
@@ -381,13 +381,27 @@ def build_anchor_sources(cs: torch.Tensor, anchor_th: float, buf: Optional[Ancho
     return buf
 
 
+def build_anchor_sources_needed(cs: torch.Tensor, anchor_th: float, cos_th: float,
+                                buf: Optional[AnchorSources] = None) -> AnchorSources:
+    """The pairs of build_anchor_sources, but only the sources the occlusion flags depend on (include/dtk.h):
+    counts = (all anchor pairs, emitted sources, queries without anchors, open queries)."""
+    N, T = cs.shape
+    if buf is None or buf.N != N or buf.T != T:
+        buf = AnchorSources(N, T, cs.device)
+    check(lib().dtk_build_anchor_sources_needed(_p(cs, torch.float32), float(anchor_th), float(cos_th), N, T,
+                                                _p(buf.n_anchors), _p(buf.pair_off), _p(buf.pair_frame), _p(buf.src_row),
+                                                _p(buf.tgt), _p(buf.out_idx), _p(buf.counts), _p(buf.scratch), _stream()))
+    return buf
+
+
 def occlusion(green: torch.Tensor, pair_off: torch.Tensor, pair_frame: torch.Tensor, traj: torch.Tensor,
-              cs: torch.Tensor, anchor_th: float, cos_th: float) -> torch.Tensor:
+              cs: torch.Tensor, anchor_th: float, cos_th: float, needed_only: bool = False) -> torch.Tensor:
+    """needed_only: green holds only what build_anchor_sources_needed listed at the same thresholds (dtk_occlusion_needed)."""
     N, T = cs.shape
     occ = torch.empty((N, T), dtype=torch.uint8, device=cs.device)
-    check(lib().dtk_occlusion(_p(green, torch.float32), _p(pair_off, torch.int32), _p(pair_frame, torch.int32),
-                              _p(traj, torch.float32), _p(cs, torch.float32), float(anchor_th), float(cos_th),
-                              _p(occ), N, T, _stream()))
+    fn = lib().dtk_occlusion_needed if needed_only else lib().dtk_occlusion
+    check(fn(_p(green, torch.float32), _p(pair_off, torch.int32), _p(pair_frame, torch.int32), _p(traj, torch.float32),
+             _p(cs, torch.float32), float(anchor_th), float(cos_th), _p(occ), N, T, _stream()))
     return occ.bool()
 
 

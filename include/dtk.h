@@ -470,11 +470,31 @@ int dtk_build_anchor_sources(const float* cs, float anchor_th, int N, int T, int
                              int32_t* pair_frame, int32_t* src_row, int32_t* tgt, int32_t* out_idx,
                              int32_t* counts, int32_t* scratch, void* stream);
 
+/* The anchor stage restricted to the maps the occlusion flags depend on (what ModelInference.infer runs).  With
+ *   anchor(n,t) = cs >= anchor_th,  low(n,t) = cs < cos_th,  undecided = !anchor && !low  (a NaN cs is undecided),
+ *   needed(n,t) = anchor || undecided,  query n OPEN = it has >= 1 anchor and >= 1 undecided frame,
+ * occ[n][t] = med > tau || low with tau = max of med over the anchor frames: an anchor frame has occ = low, a low frame
+ * occ = 1, so green[p][t] matters only for the pairs p of open queries at their needed columns t.  Exact, no approximation.
+ * n_anchors, pair_off, pair_frame, counts[0] (= P, ALL anchor pairs), counts[2] and the [P][T][2] layout of green are those
+ * of dtk_build_anchor_sources; the source lists hold (open n, anchor a of n, needed column t of n) only, sorted by a, within
+ * a by n, within a pair by t: src_row = n*T + t, tgt = a, out_idx = p*T + t.  counts[1] = emitted sources (the valid prefix
+ * of the three lists; nothing is written behind it), counts[3] = open queries.  No host sync.  Buffer sizes as above, except
+ * scratch: 2*T + 2 + N entries (N more: the per-query source count). */
+int dtk_build_anchor_sources_needed(const float* cs, float anchor_th, float cos_th, int N, int T, int32_t* n_anchors,
+                                    int32_t* pair_off, int32_t* pair_frame, int32_t* src_row, int32_t* tgt, int32_t* out_idx,
+                                    int32_t* counts, int32_t* scratch, void* stream);
+
 /* ---- K15: occlusion (models/model_inference.py:169-200) ---------------------------------------------------
  * green [P][T][2] (anchor trajectories, pair-major), pair_off [N+1], pair_frame [P] (anchor frame of pair p),
  * traj [N][T][2], cs [N][T]  ->  occ [N][T] (uint8 0/1). */
 int dtk_occlusion(const float* green, const int32_t* pair_off, const int32_t* pair_frame, const float* traj,
                   const float* cs, float anchor_th, float cos_th, uint8_t* occ, int N, int T, void* stream);
+
+/* The same flags from a green that holds only what dtk_build_anchor_sources_needed listed (same thresholds): green[p][t] is
+ * read for the pairs of open queries at their needed columns and nowhere else (the rest may be uninitialised memory);
+ * distances, ranks and medians are computed only there; the other frames get low(n,t), a query without anchors all ones. */
+int dtk_occlusion_needed(const float* green, const int32_t* pair_off, const int32_t* pair_frame, const float* traj,
+                         const float* cs, float anchor_th, float cos_th, uint8_t* occ, int N, int T, void* stream);
 
 /* ---- TAP-Vid metric counts (eval/metrics.py:7-147 for one video) ----------------------------------
  * pred_tracks / gt_tracks [N][T][2] f32 (x, y), *_occluded [N][T] (uint8 0/1), query_frame [N]; coordinates are scaled

@@ -17,7 +17,7 @@ ops.profile_enable(True)
 mi.infer(queries)
 prof = ops.profile_collect()
 ops.profile_enable(False)
-maps = N * T + int(mi.last_counts[0]) * T
+maps = N * T + int(mi.last_counts[1])   # executed maps: the first pass and the anchor sources that were emitted
 print("DTK_DEBUG", os.environ.get("DTK_DEBUG"), "maps", maps, {k: (round(v[0], 2), v[1]) for k, v in sorted(prof.items(), key=lambda kv: -kv[1][0])[:7]})
 
 import ctypes

@@ -19,6 +19,6 @@ for it in range(3):
     torch.cuda.synchronize(); t0 = time.time()
     traj, occ = mi.infer(queries)
     torch.cuda.synchronize(); dt = time.time() - t0
-    P = int(mi.last_counts[0])
-    maps = queries.shape[0] * T + P * T
-    print(f"method {method} T={T} N={queries.shape[0]} C={C} pairs={P} maps={maps} time={dt:.3f}s  maps/s={maps/dt:.0f} qpf/s={queries.shape[0]*T/dt:.1f}", flush=True)
+    P, M = int(mi.last_counts[0]), int(mi.last_counts[1])   # all anchor pairs; anchor-stage maps actually run
+    maps = queries.shape[0] * T + M
+    print(f"method {method} T={T} N={queries.shape[0]} C={C} pairs={P} anchor_maps={M} of {P * T} maps={maps} time={dt:.3f}s  maps/s={maps/dt:.0f} qpf/s={queries.shape[0]*T/dt:.1f}", flush=True)
