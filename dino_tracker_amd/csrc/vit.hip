@@ -444,8 +444,11 @@ int launch_gemm(const char* name, const GemmPath& path, const T* A, const T* W, 
         const bool ws_fits = EPI != EPI_QKV || e.S >= WS_ROWS || rows <= e.S;
         if (path.ws && K == WS_K && ws_fits) {
             const auto gr = gemm_ws_grid(N, rows);
+            // (the hand-cut form of gemm_ws_kernel gives a wave all of its 64 columns or none: N = 3 D, D, 4 D with D = 384)
             if (path.ws_v1)
                 DTK_LAUNCH(name, (gemm_ws_kernel<T, EPI, 0>), gr.first, dim3(256), 0, st, A, W, rows, N, e, gr.second);
+            else if (N % 64 != 0 || DTK_DBG(e.no_store, 128))   // (DTK_DEV bit 128: the form before the hand-cut step, for A / B)
+                DTK_LAUNCH(name, (gemm_ws_kernel<T, EPI, 3, false>), gr.first, dim3(256), 0, st, A, W, rows, N, e, gr.second);
             else
                 DTK_LAUNCH(name, (gemm_ws_kernel<T, EPI>), gr.first, dim3(256), 0, st, A, W, rows, N, e, gr.second);
             return DTK_OK;
@@ -553,7 +556,7 @@ int vit_run(const dtk_vit_model* m, const float* frames, int nframes, int video_
         const GemmPath path = gemm_path(m);
         // DTK_DEV: bits 0-1 skip the weight-stationary kernel's stores; gemm_wide_kernel: 4 no stores, 8 no main loop (pipeline fill +
         // epilogue only), 16 every stage from k = 0 (cache-hot operands)
-        const int dbg_ns = DTK_DBG(dtk_dev_flags() >> 16, 0x7f);
+        const int dbg_ns = DTK_DBG(dtk_dev_flags() >> 16, 0xff);
         bool pending = false;   // `delta` holds a residual update that the next LayerNorm (or the final update) has to apply
         bool ln1_done = false;  // the previous block's fc2 has already written this block's LayerNorm-1 rows to xn (round 6)
         auto tap = [&](int l, bool with_delta) -> int {   // dtk_vit_model.tap_out: the block output of layer l joins the mean

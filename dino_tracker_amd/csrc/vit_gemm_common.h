@@ -18,6 +18,7 @@ typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
 template <typename T> struct Vec {
     typedef T t8 __attribute__((ext_vector_type(8)));
     typedef T t4 __attribute__((ext_vector_type(4)));
+    typedef T t2 __attribute__((ext_vector_type(2)));
 };
 template <typename T> struct IsF16 { static constexpr bool value = false; };
 template <> struct IsF16<_Float16> { static constexpr bool value = true; };
@@ -47,7 +48,8 @@ struct GemmEpi {
     // EPI_GELU
     T* out;         // [M][N]
     // EPI_DELTA
-    int no_store;        // DTK_DEV builds: skip the stores of the weight-stationary kernel (DTK_DEBUG & 65536)
+    int no_store;        // DTK_DEV builds: DTK_DEBUG >> 16 -- 1 | 2: skip the stores of the weight-stationary kernel; 4 .. 16: the wide kernels;
+                         // 32 / 64 / 128: gemm_ws_kernel's clean ablations and its form before the hand-cut step (vit_gemm_ws.h)
     T* delta;       // [M][N] bf16: gamma * (A W^T + bias), added to the fp32 residual stream by the next LayerNorm
     const float* gamma;  // [N] LayerScale
     // EPI_F32 (tiled kernel only)

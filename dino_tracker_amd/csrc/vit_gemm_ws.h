@@ -1,5 +1,6 @@
 // vit_gemm_ws.h -- the weight-stationary GEMM of the ViT encoder for K = 384 (QKV, attention projection and fc1 of ViT-S).
 #pragma once
+#include <type_traits>
 #include <utility>
 #include "vit_gemm_common.h"
 
@@ -8,13 +9,21 @@ namespace {
 // ---------------------------------------------------------------------------------------------------------------
 // weight-stationary GEMM for K = 384 (QKV, attention projection and fc1 of ViT-S): C[M][N] = A[M][384] . Wt[N][384]^T
 //
-// A workgroup of two waves owns 128 output features for a chunk of token tiles; a wave keeps its 64 weight rows in
-// registers for the whole chunk (A operand of MFMA 32x32x16 bf16: 24 k-steps x 2 row tiles = 192 VGPRs) and the tokens
-// stream through a triple-buffered LDS tile of 32 tokens (24 KB) filled by LDS-DMA two steps ahead, read once per wave
-// as the B operand: one ds_read_b128 feeds two MFMAs and there is no K loop with barriers -- one barrier per 32 tokens.
+// A workgroup of four waves owns 256 output features (64 per wave) for a chunk of token tiles; a wave keeps its 64 weight rows in
+// registers for the whole chunk (A operand of MFMA 32x32x16: 24 k-steps x 2 row tiles = 192 registers, AGPRs in the V2M = 3 form)
+// and the tokens stream through a triple-buffered LDS tile of 32 tokens (24 KB) filled by LDS-DMA two steps ahead, read once per
+// wave as the B operand: one ds_read_b128 feeds two MFMAs and there is no K loop with barriers -- one barrier per 32 tokens.
 // The weight rows are permuted over the MFMA rows so that in D a lane (token j, half h) holds 16 CONSECUTIVE output
 // features (n0 + 32 t + 16 h + r): the epilogue of the previous tile (bias, GELU / Q scale / LayerScale, conversion,
-// 16-byte stores) is issued between the MFMAs of the current one.  Two workgroups share a CU (one wave per SIMD).
+// 16-byte stores) is issued between the MFMAs of the current one.  One workgroup per CU (one wave per SIMD, occupancy 1).
+//
+// The default form (V2M = 3, HC) cuts that epilogue by hand: a steady-state step is one basic block of 48 MFMAs, each followed by a
+// "slot" of the previous tile's epilogue behind a sched_barrier -- 12 slots per group of 8 values in fc1 (the four polynomial chains
+// of gelu2 side by side), the flush's four ds_read_b128 behind the first MFMA and its four stores behind the next four, the V^T
+// stores one per slot.  Stores are unconditional there: only a wave without columns (n0 >= N, a loop of its own that issues its tile
+// requests and joins the barriers) and the globally last token tile (whose epilogue runs behind the loop, predicated) can be out of
+// range; the first two steps of a chunk and the tail are peeled.  Bias and LayerScale live in registers, output addresses are a
+// base per tile plus a 32-bit lane offset.  docs/KERNELS.md, profiles/gemm_ws_epilogue_isa.md.
 // Measured alternatives (all slower on MI355X): staging the outputs through LDS for whole-line stores, one output
 // feature per lane (2-byte stores), 4 tokens x 256 B per DMA request, register-staged tiles instead of LDS-DMA.
 // ---------------------------------------------------------------------------------------------------------------
@@ -24,11 +33,21 @@ constexpr int WS_LQ = WS_KS / 4;  // LDS-DMA requests per wave per tile
 constexpr int WS_PITCH = 144;                    // staging row pitch: 128 B of payload + 16 (conflict-free 16-B accesses)
 constexpr int WS_UNIT_BYTES = WS_ROWS * WS_PITCH;  // staging unit: 32 rows x 128 B (64 bf16 or 32 fp32 outputs)
 
+// f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>): the slots of a step as compile-time constants (register arrays are
+// indexed by them, which must not depend on a loop being unrolled)
+template <class F, int... I>
+__device__ __forceinline__ void ws_for_each(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
+template <int N, class F>
+__device__ __forceinline__ void ws_for_each(F&& f) { ws_for_each(f, std::make_integer_sequence<int, N>{}); }
+
 // V2M (round 4, default 3): bit 0 = weights in AGPRs (loaded there by asm; the builtin MFMA takes them from there as they are)
 // and zero accumulators through the MFMA's C operand; bit 1 = token tiles by LDS-DMA through a buffer descriptor (scalar tile
 // offset + constant per-lane offset: 3 issue slots per request instead of ~13).  V2M = 0 is the round 1-3 form, kept for the
 // A / B measurement (DTK_VIT_GEMM_WS_V1).  Same-box A / B: proj 4.97 -> 3.62 ms, qkv 12.34 -> 12.10, fc1 14.68 -> 14.55 ms per step.
-template <typename T, int EPI, int V2M = 3>
+// HC (default with V2M = 3): the hand-cut step described above; <T, EPI, 3, false> is the form before it (DTK_DEV bit 128, and any
+// N that is not a multiple of 64).  V2M = 0 shares none of the hand-cut code: it is the bitwise reference of
+// tests/test_gpu_vit_gemm_ws_epilogue.py.
+template <typename T, int EPI, int V2M = 3, bool HC = (V2M == 3)>
 __global__ __launch_bounds__(256) void gemm_ws_kernel(const T* __restrict__ A, const T* __restrict__ Wt,
                                                       long long M, int N, GemmEpi<T> e, int tiles_per_chunk) {
     typedef typename Vec<T>::t8 T8;
@@ -36,6 +55,7 @@ __global__ __launch_bounds__(256) void gemm_ws_kernel(const T* __restrict__ A, c
     (void)sizeof(T8); (void)sizeof(T4);
     constexpr bool V2 = (V2M & 1) != 0;       // AGPR weights + zero C operand
     constexpr bool V2D = (V2M & 2) != 0;      // descriptor LDS-DMA
+    static_assert(!HC || V2M == 3, "the hand-cut step is built on the AGPR weights and the descriptor LDS-DMA");
     operand_mode<T>();
     __shared__ __attribute__((aligned(1024))) unsigned char toks[3][WS_TILE_BYTES];
     __shared__ __attribute__((aligned(16))) unsigned char stage[4][2][WS_UNIT_BYTES];  // per wave: two staging units
@@ -72,7 +92,7 @@ __global__ __launch_bounds__(256) void gemm_ws_kernel(const T* __restrict__ A, c
 #pragma unroll
             for (int ks = 0; ks < WS_KS; ++ks) asm volatile("" : "+a"(wf[t][ks]));
     }
-    {
+    if constexpr (!HC) {
         const int n = min(n0 + lane, N - 1);
         s_bias[w][lane] = e.bias ? e.bias[n] : 0.f;
         s_gamma[w][lane] = (EPI == EPI_DELTA) ? e.gamma[n] : 1.f;
@@ -131,8 +151,284 @@ __global__ __launch_bounds__(256) void gemm_ws_kernel(const T* __restrict__ A, c
 #pragma unroll
     for (int k8 = 0; k8 < 8; ++k8)
         frag_off[k8] = (unsigned)((j >> 2) * 3 * 1024 + ((((2 * k8 + h + (j >> 2)) & 15) * 4 + (j & 3)) * 16));
-    // epilogue of 8 values (row tile t, half hv of this lane's 16 features): features nb .. nb + 7
     float amax = 0.f;
+    // (DTK_DEV ablations, both forms: no_store & 32 = no stores, the values folded into `dbg_sink` so that the arithmetic stays;
+    //  & 64 = bias + convert only, stores kept.  The older & 3 clears `ok`, which skips the arithmetic sunk behind it as well.)
+    unsigned dbg_sink = 0;
+    auto dbg_fold = [&](const auto& val) {
+        unsigned b[sizeof(val) / 4];
+        __builtin_memcpy(b, &val, sizeof(val));
+#pragma unroll
+        for (unsigned i = 0; i < sizeof(val) / 4; ++i) dbg_sink |= b[i];
+    };
+    if constexpr (HC) {
+        // ------------------------------------------------------------------------------------------------------
+        // The hand-cut form.  Stores can only be out of range in a wave whose columns lie past N (constant for the launch) and in
+        // the globally last token tile, whose epilogue always runs BEHIND the loop: so idle waves get a loop of their own, the
+        // first two steps of a chunk and the tail are peeled, and a steady-state step is one basic block -- 48 MFMAs, each
+        // followed by one slice ("slot") of the previous tile's epilogue behind a sched_barrier, stores unconditional.
+        // ------------------------------------------------------------------------------------------------------
+        typedef std::integral_constant<bool, true> Yes;
+        typedef std::integral_constant<bool, false> No;
+        if (n0 >= N) {   // idle wave (last column group of N = 1152 / 384): its share of the tile requests and the barriers, nothing else
+            issue(0, 0);
+            issue(min(1, NT - 1), 1);
+            dtk_vm_wait<WS_LQ>();
+            __syncthreads();
+            int b0 = 0;
+            for (int n = 0; n + 1 < NT; n += 2) {
+                const int b1 = b0 == 2 ? 0 : b0 + 1, b2 = b1 == 2 ? 0 : b1 + 1;
+                issue(min(n + 2, NT - 1), b2);
+                dtk_vm_wait<WS_LQ>();
+                __syncthreads();
+                issue(min(n + 3, NT - 1), b0);
+                dtk_vm_wait<WS_LQ>();
+                __syncthreads();
+                b0 = b2;
+            }
+            dtk_vm_wait<0>();
+            return;
+        }
+        // bias (and LayerScale) of this lane's 2 x 16 features: registers for the whole chunk (the launcher gives this form whole
+        // 64-column waves only: N % 64 == 0)
+        float bia[2][16], gam[2][16];
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int nf = n0 + 32 * t + 16 * h + r;
+                bia[t][r] = e.bias ? e.bias[nf] : 0.f;
+                gam[t][r] = (EPI == EPI_DELTA) ? e.gamma[nf] : 1.f;
+            }
+        const bool dbg_nost = DTK_DBG(e.no_store, 3) || DTK_DBG(e.no_store, 32);   // DTK_DEV: no stores (32: the arithmetic stays live)
+        const bool dbg_noar = DTK_DBG(e.no_store, 64);                              // DTK_DEV: bias + convert only, stores kept
+        auto run = [&](auto vt_tag) {
+            constexpr bool VT = decltype(vt_tag)::value;     // a V^T wave of the QKV GEMM (which == 2)
+            constexpr bool STG = EPI != EPI_GELU && !VT;     // outputs leave as whole lines through the staging unit
+            const long long mt0 = tile0 * WS_ROWS;
+            // Output addresses: a base per tile that moves by an increment, plus 32-bit lane offsets; no multiply per store.
+            //   GELU   per-lane pointer to (token j, feature n0 + 16 h) of the epilogue's tile
+            //   DELTA  uniform pointer to (first token, n0) of the staged tile; lane offset (row, piece)
+            //   Q / K  uniform pointer to (frame, head, position of the first token) of the staged tile; a lane whose row lies behind the
+            //          frame end adds `cross` (a tile crosses at most one frame end: launch_gemm, ws_fits)
+            //   V^T    the same for the epilogue's tile, tokens along the fastest axis
+            T* op = nullptr;
+            T* up = nullptr;
+            int s0 = 0;
+            unsigned cross = 0;
+            if constexpr (EPI == EPI_GELU) op = e.out + (mt0 + j) * N + n0 + 16 * h;
+            if constexpr (EPI == EPI_DELTA) up = e.delta + mt0 * N + n0;
+            if constexpr (EPI == EPI_QKV) {
+                const int f0 = (int)(mt0 / e.S);
+                s0 = (int)(mt0 - (long long)f0 * e.S);
+                if (VT) {
+                    up = e.vt + (((size_t)f0 * e.heads + head) * 64) * e.Sp + s0;
+                    cross = (unsigned)(e.heads * 64 * e.Sp - e.S);
+                } else {
+                    up = (which == 0 ? e.q : e.k) + (((size_t)f0 * e.heads + head) * e.Sp + s0) * 64;
+                    cross = (unsigned)((e.heads * e.Sp - e.S) * 64);
+                }
+            }
+            const size_t out_step = (size_t)WS_ROWS * N;
+            unsigned char* const sw = &stage[w][0][0] + j * WS_PITCH + 32 * h;                         // staging: this lane's 16 features of token j
+            const unsigned char* const sr = &stage[w][0][0] + (lane >> 3) * WS_PITCH + (lane & 7) * 16;  // flush: row lane / 8 (+ 8 p), piece lane % 8
+            auto next_tile = [&]() {   // the output base moves on by one token tile
+                if constexpr (EPI == EPI_GELU) op += out_step;
+                if constexpr (EPI == EPI_DELTA) up += out_step;
+                if constexpr (EPI == EPI_QKV) {
+                    s0 += WS_ROWS;
+                    up += VT ? WS_ROWS : WS_ROWS * 64;
+                    if (s0 >= e.S) { s0 -= e.S; up += cross; }
+                }
+            };
+            auto st16 = [&](T* p, unsigned off, dtk_u4 val, bool ok) {   // 16 bytes to p + off elements
+                if (!dbg_nost) { if (ok) *reinterpret_cast<dtk_u4*>(p + off) = val; }
+                else dbg_fold(val);
+            };
+            // ---- the epilogue of one tile in 48 slots; PRED: stores of rows < valid only (the tail), FL: with the flush of the tile before
+            float v[8];
+            f2 sx[4], uu[4], pp[4];
+            T8 o;
+            dtk_u4 fv[4];
+            unsigned voff = 0;
+            constexpr float GC[9] = {1.112979639e-10f, -1.065557687e-08f, 4.510875158e-07f, -1.125288873e-05f, 1.868377149e-04f,
+                                     -2.217123518e-03f, 1.963194646e-02f, -1.326889843e-01f, 7.978046536e-01f};   // gelu2
+            auto flush_reads = [&]() {
+                ws_for_each<4>([&](auto p_tag) {
+                    constexpr int p = decltype(p_tag)::value;
+                    fv[p] = *reinterpret_cast<const dtk_u4*>(sr + 8 * p * WS_PITCH);
+                });
+            };
+            auto flush_store = [&](auto pred_tag, auto p_tag, int valid) {
+                constexpr int p = decltype(p_tag)::value;
+                const int row = 8 * p + (lane >> 3);
+                const bool ok = decltype(pred_tag)::value ? row < valid : true;
+                if constexpr (EPI == EPI_DELTA) st16(up, (unsigned)(row * N + (lane & 7) * 8), fv[p], ok);
+                else st16(up, (unsigned)(row * 64 + (lane & 7) * 8) + (s0 + row >= e.S ? cross : 0u), fv[p], ok);
+            };
+            auto slot = [&](auto pred_tag, auto fl_tag, const f16v (&acc)[2], auto s_tag, int valid) {
+                constexpr bool PRED = decltype(pred_tag)::value, FL = decltype(fl_tag)::value;
+                constexpr int s = decltype(s_tag)::value;
+                const bool ok = PRED ? j < valid : true;
+                if constexpr (EPI == EPI_GELU) {
+                    constexpr int u = s / 12, ph = s % 12, t = u >> 1, hv = u & 1;
+                    if (ph < 2) {
+#pragma unroll
+                        for (int r = 4 * ph; r < 4 * ph + 4; ++r) v[r] = acc[t][8 * hv + r] + bia[t][8 * hv + r];
+                        if (IsF16<T>::value) {   // the stored GELU(v): the positive part of v
+#pragma unroll
+                            for (int r = 4 * ph; r < 4 * ph + 4; r += 2) amax = fmaxf(fmaxf(amax, v[r]), v[r + 1]);
+                        }
+                    }
+                    if (dbg_noar) {
+                        if (ph == 9) {
+#pragma unroll
+                            for (int r = 0; r < 8; ++r) o[r] = (T)v[r];
+                        }
+                    } else if (ph == 2) {   // gelu2, its four chains side by side
+                        const f2 c = {4.25f, 4.25f};
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) sx[q] = __builtin_elementwise_min(__builtin_elementwise_max(f2{v[2 * q], v[2 * q + 1]}, -c), c);
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) uu[q] = sx[q] * sx[q];
+                    } else if (ph >= 3 && ph <= 6) {
+#pragma unroll
+                        for (int l = 2 * (ph - 3); l < 2 * (ph - 3) + 2; ++l)
+#pragma unroll
+                            for (int q = 0; q < 4; ++q)
+                                pp[q] = __builtin_elementwise_fma(l == 0 ? f2{GC[0], GC[0]} : pp[q], uu[q], f2{GC[l + 1], GC[l + 1]});
+                    } else if (ph == 7) {
+                        const f2 one = {1.f, 1.f};
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) pp[q] = __builtin_elementwise_min(__builtin_elementwise_max(sx[q] * pp[q], -one), one);
+                    } else if (ph == 8) {
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) {
+                            const f2 hx = f2{v[2 * q], v[2 * q + 1]} * f2{0.5f, 0.5f};
+                            uu[q] = __builtin_elementwise_fma(hx, pp[q], hx);
+                        }
+                    } else if (ph == 9) {
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) { o[2 * q] = (T)uu[q][0]; o[2 * q + 1] = (T)uu[q][1]; }
+                    }
+                    if (ph == 10) {
+                        // (staged for whole-line stores like q / k / delta, on top of this flush: fc1 14.73 against 14.47 ms per step, same
+                        //  session -- the 16-byte pieces stay; docs/NEGATIVE_RESULTS.md)
+                        st16(op, (unsigned)(32 * t + 8 * hv), __builtin_bit_cast(dtk_u4, o), ok);
+                    }
+                } else if constexpr (STG) {
+                    if constexpr (FL && s == 0) flush_reads();
+                    if constexpr (FL && s >= 1 && s <= 4) flush_store(No{}, std::integral_constant<int, s - 1>{}, WS_ROWS);
+                    constexpr int u = s / 12, ph = s % 12, t = u >> 1, hv = u & 1;
+                    if (ph & 1) {
+                        if (ph < 9) {
+                            constexpr int r0 = (ph - 1) & 7, r1 = ph & 7;   // this slot's pair of values
+                            const float v0 = acc[t][8 * hv + r0] + bia[t][8 * hv + r0], v1 = acc[t][8 * hv + r1] + bia[t][8 * hv + r1];
+                            if (EPI == EPI_QKV && IsF16<T>::value && !dbg_noar) amax = amax2(amax, v0 * qsc, v1 * qsc);
+                            if (dbg_noar) { o[r0] = (T)v0; o[r1] = (T)v1; }
+                            else if (EPI == EPI_DELTA) { o[r0] = (T)(v0 * gam[t][8 * hv + r0]); o[r1] = (T)(v1 * gam[t][8 * hv + r1]); }
+                            else { o[r0] = (T)(v0 * qsc); o[r1] = (T)(v1 * qsc); }
+                        } else if (ph == 9) {
+                            *reinterpret_cast<T8*>(sw + 64 * t + 16 * hv) = o;
+                        }
+                    }
+                } else {   // V^T[f][head][dh][s]: consecutive lanes are consecutive tokens; 2-byte stores, one per slot
+                    if (s == 0) voff = (unsigned)(16 * h * e.Sp + j) + (s0 + j >= e.S ? cross : 0u);
+                    if (s < 32) {
+                        constexpr int u = (s & 31) / 8, r = s % 8, t = u >> 1, hv = u & 1;
+                        v[r] = acc[t][8 * hv + r] + bia[t][8 * hv + r];
+                        if (IsF16<T>::value && (r & 1) && !dbg_noar) amax = amax2(amax, v[r - 1] * qsc, v[r] * qsc);
+                        const T val = (T)v[r];
+                        T* const p = up + (size_t)(32 * t + 8 * hv + r) * e.Sp;
+                        if (!dbg_nost) { if (ok) p[voff] = val; }
+                        else dbg_fold(typename Vec<T>::t2{val, val});
+                    }
+                }
+            };
+            auto tail_epi = [&](const f16v (&acc)[2], int valid) {
+                ws_for_each<2 * WS_KS>([&](auto s_tag) { slot(Yes{}, No{}, acc, s_tag, valid); });
+                if (!STG) next_tile();
+            };
+            auto tail_flush = [&](int valid) {
+                if constexpr (STG) {
+                    flush_reads();
+                    ws_for_each<4>([&](auto p_tag) { flush_store(Yes{}, p_tag, valid); });
+                    next_tile();
+                }
+            };
+            // one step: the MFMAs of the tile in `buf` into accN; PREV: behind each, a slot of the previous tile's epilogue (accP)
+            auto step = [&](auto prev_tag, auto fl_tag, int buf, f16v (&accN)[2], const f16v (&accP)[2]) {
+                constexpr bool PREV = decltype(prev_tag)::value, FL = decltype(fl_tag)::value;
+                const unsigned char* base = &toks[0][0] + buf * WS_TILE_BYTES;
+                const f16v zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};   // inline constant C
+                T8 b[3];
+                b[0] = *reinterpret_cast<const T8*>(base + frag_off[0]);
+                b[1] = *reinterpret_cast<const T8*>(base + frag_off[1]);
+                ws_for_each<2 * WS_KS>([&](auto s_tag) {
+                    constexpr int ks = decltype(s_tag)::value / 2, t = decltype(s_tag)::value % 2;
+                    if constexpr (t == 0 && ks + 2 < WS_KS)
+                        b[(ks + 2) % 3] = *reinterpret_cast<const T8*>(base + frag_off[(ks + 2) & 7] + ((ks + 2) >> 3) * 1024);
+                    // (the builtin, not an asm MFMA: see the V2M = 0 .. 3 step below)
+                    accN[t] = mfma32(wf[t][ks], b[ks % 3], ks == 0 ? zero16 : accN[t]);
+                    if constexpr (PREV) {
+                        __builtin_amdgcn_sched_barrier(0);
+                        slot(No{}, fl_tag, accP, s_tag, WS_ROWS);
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                });
+                // (staged forms: `up` follows the FLUSHED tile, two behind; the others the epilogue's tile, one behind)
+                if (STG ? FL : PREV) next_tile();
+            };
+            f16v accA[2], accB[2];
+            issue(0, 0);
+            issue(min(1, NT - 1), 1);
+            dtk_vm_wait<WS_LQ>();
+            __syncthreads();
+            int n = 0, b0 = 0;
+            auto pair = [&](auto first_tag) {
+                constexpr bool FIRST = decltype(first_tag)::value;
+                const int b1 = b0 == 2 ? 0 : b0 + 1, b2 = b1 == 2 ? 0 : b1 + 1;
+                issue(min(n + 2, NT - 1), b2);
+                if (FIRST) step(No{}, No{}, b0, accA, accB);
+                else step(Yes{}, Yes{}, b0, accA, accB);
+                dtk_vm_wait<WS_LQ>();
+                __syncthreads();
+                issue(min(n + 3, NT - 1), b0);
+                if (FIRST) step(Yes{}, No{}, b1, accB, accA);
+                else step(Yes{}, Yes{}, b1, accB, accA);
+                dtk_vm_wait<WS_LQ>();
+                __syncthreads();
+                b0 = b2;
+                n += 2;
+            };
+            if (NT >= 2) pair(Yes{});
+            while (n + 1 < NT) pair(No{});
+            const long long left = M - (tile0 + NT - 1) * WS_ROWS;   // valid rows of the chunk's last tile
+            const int valid = left < WS_ROWS ? (int)left : WS_ROWS;
+            const bool odd = n < NT;  // one more tile
+            if (odd) {
+                if (n > 0) step(Yes{}, Yes{}, b0, accA, accB);
+                else step(No{}, No{}, b0, accA, accB);
+            }
+            if (NT > 1) tail_flush(WS_ROWS);
+            // (the last tile's accumulators by VALUE: two calls of the tail on accA / accB are merged into one on a pointer, which
+            //  takes both arrays out of the registers for the whole kernel)
+            const f16v accL[2] = {odd ? accA[0] : accB[0], odd ? accA[1] : accB[1]};
+            tail_epi(accL, valid);
+            tail_flush(valid);
+        };
+        if constexpr (EPI == EPI_QKV) {
+            if (which == 2) run(Yes{});
+            else run(No{});
+        } else {
+            run(No{});
+        }
+        if (DTK_DBG(e.no_store, 32) && dbg_sink == 0x9e3779b9u) amax = 65504.f;   // (DTK_DEV: keeps the values of disabled stores live)
+        amax_report<T, EPI>(amax, e.ovf);
+        dtk_vm_wait<0>();
+        return;
+    }
+    // epilogue of 8 values (row tile t, half hv of this lane's 16 features): features nb .. nb + 7
     auto epi8 = [&](const f16v (&acc)[2], int t, int hv) {
         const int fl = 32 * t + 16 * h + 8 * hv;  // feature offset inside the wave's 64
         const int nb = n0 + fl;
@@ -147,19 +443,20 @@ __global__ __launch_bounds__(256) void gemm_ws_kernel(const T* __restrict__ A, c
 #pragma unroll
             for (int r = 0; r < 8; r += 2) {
                 if (EPI == EPI_GELU) amax = fmaxf(fmaxf(amax, v[r]), v[r + 1]);   // the stored GELU(v): the positive part of v
-                else amax = amax2(amax, v[r] * qsc, v[r + 1] * qsc);
+                else if (!DTK_DBG(e.no_store, 64)) amax = amax2(amax, v[r] * qsc, v[r + 1] * qsc);
             }
         }
         if (EPI == EPI_GELU) {
             T8 o;
 #pragma unroll
             for (int r = 0; r < 8; r += 2) {
-                const f2 g = gelu2(f2{v[r], v[r + 1]});
+                const f2 g = DTK_DBG(e.no_store, 64) ? f2{v[r], v[r + 1]} : gelu2(f2{v[r], v[r + 1]});
                 o[r] = (T)g[0];
                 o[r + 1] = (T)g[1];
             }
             // (staging the GELU output for whole-line stores measured slower than these scattered 16-byte stores)
-            if (ok) *reinterpret_cast<T8*>(e.out + m_ep * N + nb) = o;
+            if (DTK_DBG(e.no_store, 32)) dbg_fold(o);
+            else if (ok) *reinterpret_cast<T8*>(e.out + m_ep * N + nb) = o;
         } else if (EPI == EPI_DELTA) {
             const float4 g0 = *reinterpret_cast<const float4*>(&s_gamma[w][fl]), g1 = *reinterpret_cast<const float4*>(&s_gamma[w][fl + 4]);
             T8 o = {(T)(v[0] * g0.x), (T)(v[1] * g0.y), (T)(v[2] * g0.z), (T)(v[3] * g0.w),
@@ -172,7 +469,10 @@ __global__ __launch_bounds__(256) void gemm_ws_kernel(const T* __restrict__ A, c
                 // (round 6, measured and dropped: staging the wave's 64 x 32 tile transposed in LDS and flushing 8-byte pieces of four
                 //  tokens -- 8 store instructions instead of 32 -- made qkv 12.3 -> 15.7 ms per step: the 32 two-byte LDS writes sit in
                 //  the lone wave's issue stream like the stores they replace; docs/NEGATIVE_RESULTS.md)
-                if (ok) {
+                if (DTK_DBG(e.no_store, 32)) {
+#pragma unroll
+                    for (int r = 0; r < 8; r += 2) dbg_fold(typename Vec<T>::t2{(T)v[r], (T)v[r + 1]});
+                } else if (ok) {
                     T* vp = e.vt + (((size_t)f_ep * e.heads + head) * 64 + dh) * e.Sp + s_ep;
 #pragma unroll
                     for (int r = 0; r < 8; ++r) vp[(size_t)r * e.Sp] = (T)v[r];
@@ -180,7 +480,7 @@ __global__ __launch_bounds__(256) void gemm_ws_kernel(const T* __restrict__ A, c
             } else {
                 T8 o;
 #pragma unroll
-                for (int r = 0; r < 8; ++r) o[r] = (T)(v[r] * qsc);
+                for (int r = 0; r < 8; ++r) o[r] = DTK_DBG(e.no_store, 64) ? (T)v[r] : (T)(v[r] * qsc);
                 *reinterpret_cast<T8*>(&stage[w][0][0] + j * WS_PITCH + fl * 2) = o;
             }
         }
@@ -198,7 +498,8 @@ __global__ __launch_bounds__(256) void gemm_ws_kernel(const T* __restrict__ A, c
                 for (int p = 0; p < 4; ++p) {
                     const int row = 8 * p + (lane >> 3), piece = lane & 7;
                     const uint4 val = *reinterpret_cast<const uint4*>(&stage[w][u][0] + row * WS_PITCH + piece * 16);
-                    if (mt_fl + row < M) {
+                    if (DTK_DBG(e.no_store, 32)) dbg_fold(val);
+                    else if (mt_fl + row < M) {
                         if (EPI == EPI_DELTA) {
                             *reinterpret_cast<uint4*>(e.delta + (mt_fl + row) * N + n0 + piece * 8) = val;
                         } else {
@@ -287,6 +588,7 @@ __global__ __launch_bounds__(256) void gemm_ws_kernel(const T* __restrict__ A, c
         for (int u = 0; u < 4; ++u) epi8(accB, u >> 1, u & 1);
     }
     flush();
+    if (DTK_DBG(e.no_store, 32) && dbg_sink == 0x9e3779b9u) amax = 65504.f;
     amax_report<T, EPI>(amax, e.ovf);
     dtk_vm_wait<0>();
 }
