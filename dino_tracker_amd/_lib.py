@@ -79,6 +79,30 @@ class AdamArgs(ctypes.Structure):
                 ("beta1", ctypes.c_double), ("beta2", ctypes.c_double), ("eps", ctypes.c_double)]
 
 
+RAFT_SPLIT, RAFT_FP16 = 0, 1
+RAFT_ACT_NONE, RAFT_ACT_RELU, RAFT_ACT_SIGMOID, RAFT_ACT_TANH = 0, 1, 2, 3
+RAFT_NUM_CONVS = 48
+
+
+class RaftConvDesc(ctypes.Structure):
+    """struct dtk_raft_conv_desc."""
+    _fields_ = ([("w_hi", c_void_p), ("w_lo", c_void_p), ("bias", c_void_p)] +
+                [(n, ctypes.c_int32) for n in ("cin", "cout", "kh", "kw", "stride", "pad_h", "pad_w")] + [("inv_wscale", c_float)])
+
+
+class RaftConvArgs(ctypes.Structure):
+    """struct dtk_raft_conv_args: one convolution on its own (dtk_raft_conv)."""
+    _fields_ = ([("conv", RaftConvDesc)] +
+                [(n, ctypes.c_int32) for n in ("N", "H", "W", "mode", "act", "res_relu", "in_split", "reserved")] +
+                [(n, c_void_p) for n in ("in_", "in2", "out", "res", "mul", "gate")] +
+                [(n, ctypes.c_int64) for n in ("in_stride", "in2_stride", "out_stride", "res_stride", "mul_stride", "gate_stride")])
+
+
+class RaftModel(ctypes.Structure):
+    """struct dtk_raft_model."""
+    _fields_ = [("conv", RaftConvDesc * RAFT_NUM_CONVS)]
+
+
 class TrackStats(ctypes.Structure):
     """struct dtk_track_stats (host side, filled by dtk_track)."""
     _fields_ = [("sources", ctypes.c_int32), ("whole_map_tier", ctypes.c_int32), ("exact_tier", ctypes.c_int32),
@@ -227,6 +251,19 @@ SIGNATURES = {
     "dtk_resize_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     "dtk_resize_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int,
                               c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "dtk_raft_conv_packed_halves": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "dtk_raft_conv_pack": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]),
+    "dtk_raft_conv": (c_int, [ctypes.POINTER(RaftConvArgs), c_void_p]),
+    "dtk_raft_instance_norm_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "dtk_raft_instance_norm": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p, c_size_t,
+                                       c_void_p]),
+    "dtk_raft_pyramid_floats": (c_size_t, [c_int, c_int, c_int]),
+    "dtk_raft_corr_pyramid": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "dtk_raft_lookup": (c_int, [c_void_p, c_void_p, ctypes.c_int64, c_int, c_int, c_int, c_void_p, ctypes.c_int64, c_void_p]),
+    "dtk_raft_upsample": (c_int, [c_void_p, ctypes.c_int64, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "dtk_raft_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "dtk_raft_forward": (c_int, [ctypes.POINTER(RaftModel), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                 c_size_t, c_void_p]),
 }
 
 _LIB = None

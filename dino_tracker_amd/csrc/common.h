@@ -151,6 +151,18 @@ __device__ __forceinline__ dtk_u4 dtk_make_srd(const void* p) {
     return r;
 }
 
+// hi = T(v), lo = T(v - hi).  `v` is pinned as an fp32 VALUE first: with HIP's default -ffp-contract=fast the compiler otherwise
+// fuses the caller's last multiply into the conversions (v_fma_mixlo_f16: T(a * b) rounded ONCE from the exact product) for the lo
+// half while the stored hi half is T(fp32(a * b)) -- two different hi's wherever a * b sits within fp32 rounding of a 16-bit
+// midpoint (one value in 2^13), and there hi + lo is off by a whole 16-bit ulp.  Found by the stand-alone attention test: median
+// error 1e-7, five outputs of 115 200 off by 2^-13 .. 2^-10.
+template <typename T>
+__device__ __forceinline__ void split2(float v, T& hi, T& lo) {
+    asm volatile("" : "+v"(v));
+    hi = (T)v;
+    lo = (T)(v - (float)hi);
+}
+
 // Zero `bytes` (a multiple of 4, `p` 4-byte aligned) with a KERNEL.  For launches that may be captured into a graph (the training
 // iteration, trainer.GraphedIteration): a hipMemsetAsync captured as a memset node was observed NOT to clear its range on replays
 // on this stack (round 6: the contrastive backward's |G| maximum started from the previous replay's bits -- gradients of 1e28 --

@@ -7,17 +7,20 @@
   the minimum-length compaction, on `dtk_flow_traj_start` / `dtk_flow_traj_emit`.  One host read per starting frame (the row
   count that sizes the block); the blocks are concatenated in start order, which is the reference's row order.
 * `extract_trajectories` -- the whole script for a video and a flow network `flow_fn(src, dst) -> flow`, batched as the
-  reference batches RAFT.  `torchvision_raft` makes such a function from torchvision's raft_large.
+  reference batches RAFT.  `raft.raft_flow_fn` makes such a function from this library's RAFT-large (dtk_raft_forward) and a
+  weights file; `torchvision_raft` makes one from torchvision's raft_large.
 
 The arithmetic of the device entries is written out in include/dtk.h; tests/traj_ref.py restates it with one ATen operation per
 step and the GPU tests ask for the same bits.
 
 Command line (the reference script's flags, plus --flows-path):
     python -m dino_tracker_amd.flow_trajectories --frames-path F --output-path O [--infer-res-size H W] [--threshold 1]
-        [--min-trajectory-length 2] [--filter-using-direct-flow --direct-flow-threshold X] [--flows-path P]
+        [--min-trajectory-length 2] [--filter-using-direct-flow --direct-flow-threshold X] [--flows-path P] [--raft-weights W]
 --flows-path reads a torch.save'd dict {"forward": [T - 1, 2, h, w], "backward": [T - 1, 2, h, w][, "direct": a list with, per
 starting frame, (forward, backward) flows [T - 1 - s, 2, h, w] to every later frame]} instead of running a flow network, so
 torchvision is not needed; --frames-path may then be omitted.
+--raft-weights W (or the environment variable DTK_RAFT_WEIGHTS) runs the device RAFT-large (dino_tracker_amd.raft) on a state dict
+with torchvision's raft_large key names; without either the flows come from torchvision_raft as before.
 """
 from __future__ import annotations
 
@@ -150,8 +153,9 @@ def torchvision_raft(device="cuda:0", num_flow_updates: int = 24) -> FlowFn:
 
 def run(frames_path: Optional[str], output_path: str, infer_res_size=None, threshold: float = 1.0, min_trajectory_length: int = 2,
         filter_using_direct_flow: bool = False, direct_flow_threshold: Optional[float] = None, flows_path: Optional[str] = None,
-        device="cuda:0") -> torch.Tensor:
-    """save_trajectories: writes the CPU [N, T, 2] tensor to output_path and prints the reference's line."""
+        device="cuda:0", raft_weights=None) -> torch.Tensor:
+    """save_trajectories: writes the CPU [N, T, 2] tensor to output_path and prints the reference's line.  raft_weights (a state
+    dict or a path; default: the environment variable DTK_RAFT_WEIGHTS) selects the device RAFT-large for the flows."""
     if filter_using_direct_flow and direct_flow_threshold is None:
         raise ValueError("--filter-using-direct-flow needs --direct-flow-threshold")
     if flows_path is not None:
@@ -168,7 +172,14 @@ def run(frames_path: Optional[str], output_path: str, infer_res_size=None, thres
             raise ValueError("--frames-path or --flows-path is required")
         from .train import load_video
         video = load_video(frames_path, resize=tuple(infer_res_size) if infer_res_size is not None else None, device=device)
-        traj = extract_trajectories(video, torchvision_raft(device), threshold, min_trajectory_length, filter_using_direct_flow,
+        if raft_weights is None:
+            raft_weights = os.environ.get("DTK_RAFT_WEIGHTS") or None
+        if raft_weights is not None:
+            from .raft import RaftLarge, raft_flow_fn
+            flow_fn = raft_flow_fn(RaftLarge(raft_weights, device))
+        else:
+            flow_fn = torchvision_raft(device)
+        traj = extract_trajectories(video, flow_fn, threshold, min_trajectory_length, filter_using_direct_flow,
                                     direct_flow_threshold, device)
     traj = traj.cpu()
     d = os.path.dirname(output_path)
@@ -189,9 +200,11 @@ def main(argv=None):
     ap.add_argument("--filter-using-direct-flow", action="store_true", default=False, help="Filter using direct flow")
     ap.add_argument("--direct-flow-threshold", type=float, default=None, help="Threshold for direct flow error")
     ap.add_argument("--flows-path", type=str, default=None, help="torch.save'd flows to chain instead of running RAFT")
+    ap.add_argument("--raft-weights", type=str, default=None,
+                    help="raft_large state dict for the device RAFT (default: $DTK_RAFT_WEIGHTS, else torchvision)")
     a = ap.parse_args(argv)
     run(a.frames_path, a.output_path, a.infer_res_size, a.threshold, a.min_trajectory_length, a.filter_using_direct_flow,
-        a.direct_flow_threshold, a.flows_path)
+        a.direct_flow_threshold, a.flows_path, raft_weights=a.raft_weights)
 
 
 if __name__ == "__main__":

@@ -194,8 +194,18 @@ def run_masks(config_path: str, data_path: str, device="cuda:0", from_video: boo
     return fg_mask.run(emb_path, h, w, config["masks_path"], fg_mask_threshold=thr, device=device)
 
 
-def run_all(config_path: str, data_path: str, device="cuda:0", make_masks: bool = False):
-    """main_preprocessing.py step 4 + main_dino_bb_preprocessing.py steps 1, 3, 4 on the reference's file layout."""
+def _make_trajectories(config, path: str, direct: bool, raft_weights, device) -> None:
+    """main_preprocessing.py step 1 (and its unfiltered twin) on the device RAFT: extract_trajectories with the config's settings."""
+    from . import flow_trajectories
+    flow_trajectories.run(config["video_folder"], path, (config["video_resh"], config["video_resw"]), config["threshold"],
+                          config["min_trajectory_length"], direct, config["direct_flow_threshold"] if direct else None,
+                          device=device, raft_weights=raft_weights)
+
+
+def run_all(config_path: str, data_path: str, device="cuda:0", make_masks: bool = False, raft_weights=None):
+    """main_preprocessing.py step 4 + main_dino_bb_preprocessing.py steps 1, 3, 4 on the reference's file layout.  With
+    raft_weights (or the environment variable DTK_RAFT_WEIGHTS) a missing trajectory file is made here by the device RAFT-large
+    (main_preprocessing.py step 1); without it a missing file is an error, as before."""
     import yaml
     from .best_buddies import compute_bb_nms_all, extract_best_buddies
     from .train import load_masks
@@ -203,6 +213,11 @@ def run_all(config_path: str, data_path: str, device="cuda:0", make_masks: bool 
     with open(config_path) as fh:
         config = add_config_paths(data_path, yaml.safe_load(fh.read()))
     extract = "preprocessing/extract_trajectories.py (or python -m dino_tracker_amd.flow_trajectories)"
+    raft_weights = raft_weights if raft_weights is not None else (os.environ.get("DTK_RAFT_WEIGHTS") or None)
+    if raft_weights is not None:
+        for key, direct in (("trajectories_file", True), ("unfiltered_trajectories_file", False)):
+            if not os.path.exists(config[key]):
+                _make_trajectories(config, config[key], direct, raft_weights, device)
     traj_path = _need(config["trajectories_file"], extract + " with --filter-using-direct-flow")
     unfiltered_path = _need(config["unfiltered_trajectories_file"], extract + " without --filter-using-direct-flow")
     if make_masks and not os.path.exists(config["masks_path"]):
@@ -262,8 +277,10 @@ def main(argv=None):
             run_masks(a.config, a.data_path)
             return
         ap.add_argument("--make-masks", action="store_true")
+        ap.add_argument("--raft-weights", type=str, default=None,
+                        help="raft_large state dict: make missing trajectory files with the device RAFT (default: $DTK_RAFT_WEIGHTS)")
         a = ap.parse_args(rest)
-        run_all(a.config, a.data_path, make_masks=a.make_masks)
+        run_all(a.config, a.data_path, make_masks=a.make_masks, raft_weights=a.raft_weights)
 
 
 if __name__ == "__main__":

@@ -168,3 +168,30 @@ def make_outlier_vit_weights(scale_fc2: float = 300.0, model_name: str = "dinov2
     sd["blocks.3.mlp.fc2.weight"] *= scale_fc2
     return sd
 
+
+
+def make_raft_weights(seed: int = 0) -> Dict[str, torch.Tensor]:
+    """A raft_large state dict (torchvision key names, dino_tracker_amd.raft.expected_keys) with seeded weights, for tests and timing.
+
+    torchvision's initialisation: Kaiming normal (fan-out, ReLU gain) convolution weights, biases uniform in +-1 / sqrt(fan_in);
+    the BatchNorms get non-trivial affine parameters and running statistics so that folding them is not a no-op.
+    TWO convolutions are scaled down: the last flow-head convolution by 0.01 and the feature encoder's output convolution by
+    0.1.  Without that the recurrence of an untrained network is chaotic (the flow reaches ~150 px after one update and fp32
+    differs from float64 by hundreds of px after 24), and such a network cannot be compared with anything; with it the flow
+    grows by a fraction of a pixel per update and fp32 stays ~1e-5 px from float64."""
+    from .raft import BN_FIELDS, raft_large_convs
+    g = torch.Generator().manual_seed(seed)
+    sd: Dict[str, torch.Tensor] = {}
+    for s in raft_large_convs():
+        fan_out, fan_in = s.cout * s.kh * s.kw, s.cin * s.kh * s.kw
+        w = torch.randn(s.cout, s.cin, s.kh, s.kw, generator=g) * (2.0 / fan_out) ** 0.5
+        b = (torch.rand(s.cout, generator=g) * 2 - 1) / fan_in ** 0.5
+        shrink = {"update_block.flow_head.conv2": 0.01, "feature_encoder.conv": 0.1}.get(s.key, 1.0)
+        sd[f"{s.key}.weight"], sd[f"{s.key}.bias"] = w * shrink, b * shrink
+        if s.bn is not None:
+            vals = (0.8 + 0.4 * torch.rand(s.cout, generator=g), 0.1 * torch.randn(s.cout, generator=g),
+                    0.1 * torch.randn(s.cout, generator=g), 0.5 + torch.rand(s.cout, generator=g))
+            for f, v in zip(BN_FIELDS, vals):
+                sd[f"{s.bn}.{f}"] = v
+            sd[f"{s.bn}.num_batches_tracked"] = torch.tensor(100, dtype=torch.int64)
+    return sd

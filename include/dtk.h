@@ -786,6 +786,108 @@ int dtk_resize_u8(const uint8_t* in, int32_t N, int32_t H, int32_t W, int32_t C,
                   const float* u8_to_f32, int32_t out_form, int32_t options, void* out, void* workspace, size_t workspace_bytes,
                   void* stream);
 
+/* ---- RAFT-large optical flow (torchvision.models.optical_flow.raft_large, restated from the published definition: the one step
+ * of preprocessing/extract_trajectories.py the entries above did not cover) ----------------------------------------------------
+ * Every activation is fp32 NHWC: [images][rows][columns][channels].  A tensor argument may be a channel SLICE of a wider tensor:
+ * a pointer to the slice's first channel of pixel 0 plus the channel stride (floats from one pixel to the next).
+ *
+ * Operand modes (`mode`), for the convolutions and the correlation:
+ *   DTK_RAFT_SPLIT  every operand x is carried as hi + lo, hi = fp16(x), lo = fp16(x - hi), and every product a b is formed as
+ *                   a_hi b_hi + a_hi b_lo + a_lo b_hi on the matrix cores with fp32 accumulation.  Representation: hi + lo equals
+ *                   x to max(2^-22 |x|, 2^-25) for |x| < 65504; the dropped a_lo b_lo is below 2^-22 |a b|.  Weights are packed
+ *                   multiplied by the power of two `wscale` (the accumulator is multiplied by inv_wscale = 1 / wscale) so that
+ *                   their lo halves stay normal numbers: for 2^-14 <= |w wscale| < 65504 the weight term is 2^-22 |w|.
+ *   DTK_RAFT_FP16   the hi halves only: operands rounded to fp16 (2^-11 relative), fp32 accumulation.
+ *
+ * dtk_raft_conv_pack: fp32 weights [cout][cin][kh][kw] -> the planes w_hi / w_lo, dtk_raft_conv_packed_halves(cout, cin, kh, kw)
+ *   fp16 values each: [cout padded to 64][kh kw][cin padded to 32] of w * wscale, zeros in the padding.
+ * dtk_raft_conv: out[n][oy][ox][co] = E(inv_wscale * sum_{ky, kx, ci} in[n][oy stride - pad_h + ky][ox stride - pad_w + kx][ci]
+ *   w[co][ci][ky][kx] + bias[co]), zeros outside the image, output size floor((H + 2 pad_h - kh) / stride) + 1 (W alike).  The
+ *   input channels ci < in_split come from `in`, the others from `in2` (in2 = NULL: all from `in`; in_split is a multiple of 32).
+ *   The epilogue E, in this order:  t = act(.) (none / max(t, 0) / sigmoid / tanh);  mul: t = t * mul;  gate: t = (1 - gate) * out_old
+ *   + gate * t with out_old the value `out` held (the GRU update, in place);  res: t = t + res, then max(t, 0) when res_relu.  `res`
+ *   may be `out` itself (flow += delta).  sigmoid and tanh are within 4.8e-7 absolute of the exact functions.  Only the `cout`
+ *   channels of the output slice are written.  The sum runs over 32-channel chunks of one tap at a time, taps in (ky, kx) order.
+ * dtk_raft_instance_norm (InstanceNorm2d, no affine, biased variance): y = (x - mean) / sqrt(var + eps) per image and channel;
+ *   relu: y = max(y, 0);  res != NULL: y = max(res + y, 0).  out may be x.  Two launches, no atomics: the statistics are partial
+ *   (count, mean, M2) per pixel chunk, combined in chunk order in float64 by every block alike.  C <= 256.
+ * dtk_raft_corr_pyramid: f1, f2 [N][h w][C] (C a multiple of 32) -> pyramid: level 0 [N][h w][h][w] with
+ *   corr[n][i][j] = <f1[n][i], f2[n][j]> / sqrt(C) in the operand mode, then levels 1 .. 3 [N][h w][h_l][w_l], h_l = floor(h_{l-1} /
+ *   2): ((a + b) + (c + d)) * 0.25 of the 2 x 2 block (top-left, top-right, bottom-left, bottom-right), the odd last row / column
+ *   dropped.  The levels follow each other in memory; dtk_raft_pyramid_floats(N, h, w) floats in all.  h, w >= 16.
+ * dtk_raft_lookup: flow slices [N h w][2] (x, y) -> out slices [N h w][324].  For level l: x = (column + flow_x) / 2^l,
+ *   y = (row + flow_y) / 2^l;  x0 = floor(x), fx = x - x0 (y alike).  Channel 81 l + 9 a + b reads level l's map of the cell at
+ *   (x + a - 4, y + b - 4) -- the SLOW window index moves x, upstream's order --: corners (X, Y), (X + 1, Y), (X, Y + 1),
+ *   (X + 1, Y + 1), X = x0 + a - 4, Y = y0 + b - 4, weights (1 - fx)(1 - fy), fx (1 - fy), (1 - fx) fy, fx fy, the four products
+ *   summed in that order from zero; a corner outside the map contributes zero.
+ * dtk_raft_upsample: mask [N h w][576] (channel 64 k + 8 dy + dx), flow slices -> out [N][2][8 h][8 w]:
+ *   out[n][c][8 y + dy][8 x + dx] = sum_k softmax_k(mask) * 8 flow_c(y + k / 3 - 1, x + k % 3 - 1), zero flow outside the map;
+ *   softmax as exp(mask_k - max) / sum, exp within 4.8e-7 relative, sums over k = 0 .. 8 in order.
+ *
+ * dtk_raft_forward: image1, image2 [N][3][H][W] fp32 in [-1, 1] -> flow_out [N][2][H][W], the LAST of num_flow_updates
+ *   predictions.  model->conv[k] are the network's convolutions in the order of the DTK_RAFT_* indices below (an encoder's 16:
+ *   stem; layer1 block 1 conv 1, 2; block 2 conv 1, 2; layer2 block 1 conv 1, 2, downsample; block 2 conv 1, 2; layer3 alike;
+ *   output).  The feature encoder normalises with dtk_raft_instance_norm (eps 1e-5); the context encoder's BatchNorms are folded
+ *   into its convolutions by the caller, and its output convolution is given as two (hidden half: tanh; context half: ReLU).
+ *   The mask predictor's 0.25 is folded into its last convolution by the caller.  flow is updated as flow += delta.
+ *   Refused with DTK_E_INVALID before anything is written: H or W not divisible by 8, a feature map below 16 x 16, host or null
+ *   pointers; a short workspace with DTK_E_WORKSPACE.  dtk_raft_workspace_bytes(N, H, W): the encoder activations (three
+ *   buffers of 2 N (H / 2)(W / 2) 64 floats), the update block's buffers and the pyramid (N (h w) (h w + ...) floats: ~220 MB per
+ *   pair at 480 x 856 -- the caller bounds its batch by this); 0 for sizes the call refuses. */
+#define DTK_RAFT_SPLIT 0
+#define DTK_RAFT_FP16 1
+#define DTK_RAFT_ACT_NONE 0
+#define DTK_RAFT_ACT_RELU 1
+#define DTK_RAFT_ACT_SIGMOID 2
+#define DTK_RAFT_ACT_TANH 3
+#define DTK_RAFT_FEATURE 0          /* .. 15 */
+#define DTK_RAFT_CONTEXT 16         /* .. 30, then the two halves of the output convolution */
+#define DTK_RAFT_CONTEXT_HIDDEN 31
+#define DTK_RAFT_CONTEXT_CONTEXT 32
+#define DTK_RAFT_MOTION 33          /* convcorr1, convcorr2, convflow1, convflow2, conv */
+#define DTK_RAFT_GRU 38             /* convgru1 z, r, q; convgru2 z, r, q */
+#define DTK_RAFT_FLOW_HEAD 44       /* conv1, conv2 */
+#define DTK_RAFT_MASK 46            /* the 3 x 3 convolution, the 1 x 1 convolution (x 0.25 folded) */
+#define DTK_RAFT_NUM_CONVS 48
+typedef struct dtk_raft_conv_desc {
+    const void* w_hi;   /* dtk_raft_conv_pack's planes; w_lo may be NULL for DTK_RAFT_FP16 */
+    const void* w_lo;
+    const float* bias;  /* [cout] */
+    int32_t cin, cout, kh, kw, stride, pad_h, pad_w;
+    float inv_wscale;
+} dtk_raft_conv_desc;
+typedef struct dtk_raft_conv_args {
+    dtk_raft_conv_desc conv;
+    int32_t N, H, W, mode, act, res_relu, in_split, reserved;
+    const float* in;
+    const float* in2;
+    float* out;
+    const float* res;
+    const float* mul;
+    const float* gate;
+    int64_t in_stride, in2_stride, out_stride, res_stride, mul_stride, gate_stride;
+} dtk_raft_conv_args;
+typedef struct dtk_raft_model {
+    dtk_raft_conv_desc conv[DTK_RAFT_NUM_CONVS];
+} dtk_raft_model;
+size_t dtk_raft_conv_packed_halves(int32_t cout, int32_t cin, int32_t kh, int32_t kw);
+int dtk_raft_conv_pack(const float* w, int32_t cout, int32_t cin, int32_t kh, int32_t kw, float wscale, void* w_hi, void* w_lo,
+                       void* stream);
+int dtk_raft_conv(const dtk_raft_conv_args* args, void* stream);
+size_t dtk_raft_instance_norm_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t C);
+int dtk_raft_instance_norm(const float* x, const float* res, float* out, int32_t N, int32_t H, int32_t W, int32_t C, float eps,
+                           int32_t relu, void* workspace, size_t workspace_bytes, void* stream);
+size_t dtk_raft_pyramid_floats(int32_t N, int32_t h, int32_t w);
+int dtk_raft_corr_pyramid(const float* f1, const float* f2, int32_t N, int32_t h, int32_t w, int32_t C, int32_t mode, float* pyramid,
+                          void* stream);
+int dtk_raft_lookup(const float* pyramid, const float* flow, int64_t flow_stride, int32_t N, int32_t h, int32_t w, float* out,
+                    int64_t out_stride, void* stream);
+int dtk_raft_upsample(const float* flow, int64_t flow_stride, const float* mask, int32_t N, int32_t h, int32_t w, float* out,
+                      void* stream);
+size_t dtk_raft_workspace_bytes(int32_t N, int32_t H, int32_t W);
+int dtk_raft_forward(const dtk_raft_model* model, const float* image1, const float* image2, int32_t N, int32_t H, int32_t W,
+                     int32_t num_flow_updates, int32_t mode, float* flow_out, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
