@@ -8,7 +8,7 @@
 //   gemm_tiled_kernel   (vit_gemm_tiled.h) C = A W^T on MFMA 16x16x32 (fp32 accumulate), 128x128 tiles, LDS double-buffered, with
 //                       fused epilogues: QKV split (Q pre-scaled by log2(e)/sqrt(d), V written transposed), GELU,
 //                       LayerScale + residual add into the fp32 stream.  The forms the blocks run on: vit_gemm_ws.h (K = 384,
-//                       weight-stationary), vit_gemm_wide.h (LDS-DMA pipelines), vit_split.h (the escalated precision);
+//                       weight-stationary), vit_gemm_ws_ln.h (the attention projection at D = 384 with LayerNorm-2), vit_gemm_wide.h (LDS-DMA pipelines), vit_split.h (the escalated precision);
 //                       launch_gemm / launch_gemm_split below choose among them.
 //   attention4_kernel   (vit_attention4.h; round 4) flash attention, d_head = 64: S^T = K Q^T and O^T = V^T P^T on MFMA 32x32x16
 //                       so that every per-query quantity is lane-local; K / V^T tiles by LDS-DMA into XOR-swizzled images;
@@ -29,6 +29,7 @@
 #include "vit_gemm_common.h"
 #include "vit_gemm_tiled.h"
 #include "vit_gemm_ws.h"
+#include "vit_gemm_ws_ln.h"
 #include "vit_gemm_wide.h"
 #include "vit_split.h"
 
@@ -415,17 +416,20 @@ struct GemmPath {
     bool ws_v1;    // DTK_VIT_GEMM_WS_V1: the round 1-3 form of the weight-stationary kernel (A / B)
     bool wide_v1;  // DTK_VIT_GEMM_WIDE_V1: the LDS-DMA kernels (split one included) without half-step prefetch / staged epilogues (A / B)
     bool fc2_ln;   // fc2 of a block may carry the next block's LayerNorm-1 (vit_run: when that block exists and is a fast one)
+    bool proj_ln;  // the attention projection carries its block's LayerNorm-2 (gemm_ws_ln_kernel); every A / B switch turns it off
 };
 inline GemmPath gemm_path(int D, int f) {
     const bool tiled = (f & DTK_VIT_TILED_GEMMS) != 0, ws = !tiled && D == WS_K, wide_v1 = (f & DTK_VIT_GEMM_WIDE_V1) != 0;
     static_assert(WS_K == WD_N, "fc2 of the weight-stationary width is gemm_wide_delta_kernel's shape");
-    return {tiled, ws, !tiled && D % W2_N == 0, (f & DTK_VIT_GEMM_WS_V1) != 0, wide_v1, ws && !wide_v1 && !(f & DTK_VIT_NO_LN_FUSION)};
+    const bool ws_v1 = (f & DTK_VIT_GEMM_WS_V1) != 0, fc2_ln = ws && !wide_v1 && !(f & DTK_VIT_NO_LN_FUSION);
+    return {tiled, ws, !tiled && D % W2_N == 0, ws_v1, wide_v1, fc2_ln, fc2_ln && !ws_v1};
 }
 inline GemmPath gemm_path(const dtk_vit_model* m) { return gemm_path(m->D, m->flags); }
 
 // One GEMM of a fast block, C[rows][N] = A[rows][K] . W[N][K]^T with epilogue EPI.  First match wins:
 //
 //   EPI_F32 (the qkv facet)             gemm_tiled_kernel<T, EPI_F32>, always
+//   path.ws, N = K = 384, e.ln_out set  gemm_ws_ln_kernel<T>             (proj + LayerNorm-2)           gemm_ws_ln_grid     x 256
 //   path.ws, K = 384 (qkv, proj, fc1)   gemm_ws_kernel<T, EPI>            (ws_v1: <T, EPI, 0>)           gemm_ws_grid(N)     x 256
 //                                       (not the qkv of SEVERAL frames shorter than its 32-row tile, S < 32: those fall through to the last line)
 //   path.ws, K != 384 (fc2: N = 384)    gemm_wide_delta_kernel<T>         (wide_v1: <T, false>;          rows / 256          x 512
@@ -433,7 +437,8 @@ inline GemmPath gemm_path(const dtk_vit_model* m) { return gemm_path(m->D, m->fl
 //   path.wide                           gemm_wide_kernel<T, EPI>          (wide_v1: <T, EPI, false>)     gemm_wide_grid(N)   x 512
 //   otherwise                           gemm_tiled_kernel<T, EPI>                                        gemm_grid(N)        x 256
 //
-// (path.ws and path.wide exclude each other: 384 is not a multiple of 256.  The caller sets e.ln_* only under path.fc2_ln.)
+// (path.ws and path.wide exclude each other: 384 is not a multiple of 256.  The caller sets e.ln_* only under path.fc2_ln (fc2) /
+//  path.proj_ln (proj).)
 template <typename T, int EPI>
 int launch_gemm(const char* name, const GemmPath& path, const T* A, const T* W, long long rows, int N, int K, const GemmEpi<T>& e,
                 hipStream_t st) {
@@ -442,6 +447,13 @@ int launch_gemm(const char* name, const GemmPath& path, const T* A, const T* W, 
         //  SEVERAL shorter frames -- under 49 x 49 pixels -- put Q / K rows into the padding of the wrong frame; the tiled kernel divides
         //  per row.)
         const bool ws_fits = EPI != EPI_QKV || e.S >= WS_ROWS || rows <= e.S;
+        if constexpr (EPI == EPI_DELTA) {
+            if (path.ws && K == WS_K && N == WS_K && e.ln_out) {
+                const auto gr = gemm_ws_ln_grid(rows);
+                DTK_LAUNCH(name, (gemm_ws_ln_kernel<T>), gr.first, dim3(256), 0, st, A, W, rows, e, gr.second);
+                return DTK_OK;
+            }
+        }
         if (path.ws && K == WS_K && ws_fits) {
             const auto gr = gemm_ws_grid(N, rows);
             // (the hand-cut form of gemm_ws_kernel gives a wave all of its 64 columns or none: N = 3 D, D, 4 D with D = 384)
@@ -628,9 +640,13 @@ int vit_run(const dtk_vit_model* m, const float* frames, int nframes, int video_
             if (attention_launch(q, k, vt, ao, S, Sp, m->heads, D, nf * m->heads, (m->flags & DTK_VIT_ATTENTION_V4) != 0, st)) return DTK_E_HIP;
             e = GemmEpi<T>{};
             e.bias = L.proj_b; e.delta = delta; e.gamma = L.ls1; e.no_store = dbg_ns;
+            // LayerNorm-2 runs inside the projection's epilogue (gemm_ws_ln_kernel: x += update, xn = the normalised rows; the update is
+            // not stored) -- `pending` / `ln1_done` speak of fc2's update and LayerNorm-1 only, and stay as they are
+            if (path.proj_ln) { e.ln_x = x; e.ln_w = L.ln2_w; e.ln_b = L.ln2_b; e.ln_out = xn; e.ln_eps = m->ln_eps; e.ln_ovf = ovf; }
             if (launch_gemm<T, EPI_DELTA>("vit_gemm_proj", path, ao, proj_w, rows, D, D, e, st)) return DTK_E_HIP;
-            DTK_LAUNCH("vit_layernorm", layernorm_kernel<T>, dim3(dtk_cdiv(rows, 4)), dim3(256), 0, st, x, (const T*)delta,
-                       L.ln2_w, L.ln2_b, xn, rows, D, m->ln_eps, ovf);
+            if (!path.proj_ln)
+                DTK_LAUNCH("vit_layernorm", layernorm_kernel<T>, dim3(dtk_cdiv(rows, 4)), dim3(256), 0, st, x, (const T*)delta,
+                           L.ln2_w, L.ln2_b, xn, rows, D, m->ln_eps, ovf);
             e = GemmEpi<T>{};
             e.bias = L.fc1_b; e.out = hid; e.no_store = dbg_ns; e.ovf = epi_ovf;
             if (launch_gemm<T, EPI_GELU>("vit_gemm_fc1", path, xn, fc1_w, rows, 4 * D, D, e, st)) return DTK_E_HIP;
@@ -727,8 +743,9 @@ int vit_gemm_stage(const dtk_vit_gemm_args* g, int N, int K, hipStream_t st) {
             return launch_gemm<T, EPI_GELU>("vit_gemm_fc1", path, A, W, g->rows, N, K, e, st);
         default:
             e.delta = reinterpret_cast<T*>(g->out); e.gamma = g->gamma;
-            if (g->ln_out) {   // the next block's LayerNorm inside fc2's epilogue: where vit_run fuses it, nowhere else
-                DTK_REQUIRE(g->role == DTK_VIT_GEMM_FC2 && path.fc2_ln, "dtk_vit_gemm: the fused LayerNorm is fc2's at D = 384 without TILED_GEMMS / GEMM_WIDE_V1 / NO_LN_FUSION");
+            if (g->ln_out) {   // the LayerNorm inside fc2's (the next block's) or the projection's (LayerNorm-2) epilogue: where vit_run fuses it, nowhere else
+                DTK_REQUIRE(g->role == DTK_VIT_GEMM_FC2 ? path.fc2_ln : path.proj_ln,
+                            "dtk_vit_gemm: the fused LayerNorm is fc2's or the projection's at D = 384 without TILED_GEMMS / GEMM_WIDE_V1 / NO_LN_FUSION (the projection's: nor GEMM_WS_V1)");
                 DTK_REQUIRE(g->ln_x && g->ln_w && g->ln_b, "dtk_vit_gemm: the fused LayerNorm needs ln_x, ln_w and ln_b");
                 e.ln_x = g->ln_x; e.ln_w = g->ln_w; e.ln_b = g->ln_b; e.ln_out = reinterpret_cast<T*>(g->ln_out); e.ln_eps = g->ln_eps;
                 e.ln_ovf = g->ovf;

@@ -83,7 +83,7 @@ class VitExtractor(nn.Module):
         self.attention_v2 = False       # retired: kept because bench.py assigns it on every run; True is refused where the flags are built
         self.attention_v4 = os.environ.get("DTK_VIT_ATTENTION_V4", "0") == "1"   # rounds 4-5: 64 queries per wave (round 6: 128; A / B)
         self.gemm_ws_v1 = False         # the round 1-3 form of the K = 384 weight-stationary GEMMs (A / B measurement)
-        self.no_ln_fusion = os.environ.get("DTK_VIT_NO_LN_FUSION", "0") == "1"   # D = 384: LayerNorm-1 of the next block as its own launch (A / B)
+        self.no_ln_fusion = os.environ.get("DTK_VIT_NO_LN_FUSION", "0") == "1"   # D = 384: both fused LayerNorms (LayerNorm-2 in the projection, LayerNorm-1 of the next block in fc2) as launches of their own (A / B)
         self.gemm_wide_v1 = os.environ.get("DTK_VIT_GEMM_WIDE_V1", "0") == "1"   # the LDS-DMA GEMMs with round 5's direct-store epilogues (A / B; bit-identical)
         self.frame_batch = 0            # frames per pass of the encoder; 0 = the library's default
         if model_name not in VIT_CONFIGS:

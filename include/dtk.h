@@ -130,8 +130,9 @@ typedef struct dtk_vit_model {
 #define DTK_VIT_GEMM_WS_V1 16   /* the K = 384 weight-stationary GEMMs in their round 1-3 form (A / B measurement, cross-check) */
 #define DTK_VIT_ATTENTION_V4 32 /* attention on the round-4/5 kernel (one wave per SIMD, 64 queries per wave: csrc/vit_attention4.h) instead of
                                  * round 6's 128 queries per wave (csrc/vit_attention6.h): A / B measurement, cross-check */
-#define DTK_VIT_NO_LN_FUSION 128 /* D = 384: keep the LayerNorm of the next block a launch of its own instead of running it inside fc2's
-                                  * epilogue (A / B measurement, cross-check: the results are bit-identical) */
+#define DTK_VIT_NO_LN_FUSION 128 /* D = 384: keep both LayerNorms launches of their own instead of running LayerNorm-2 inside the attention
+                                  * projection's epilogue and the LayerNorm of the next block inside fc2's (A / B measurement, cross-check:
+                                  * the results are bit-identical) */
 #define DTK_VIT_GEMM_WIDE_V1 64 /* the LDS-DMA GEMMs (256 x 256 tiles of D = 768 / 1024, fc2 of D = 384, the split-operand GEMMs) in their
                                  * round 4-5 form: 8-byte stores straight from the D tiles instead of whole rows through LDS, fragments read
                                  * at the top of every k-step (A / B measurement, cross-check: the results are bit-identical) */
@@ -174,7 +175,9 @@ int dtk_vit_attention_split(const void* q_hi, const void* q_lo, const void* k_hi
  *   DTK_VIT_GEMM_QKV        3D x D    q / k [rows / S][D / 64][Sp][64], vt [rows / S][D / 64][64][Sp]; q scaled by log2(e) / 8.  rows is a
  *                                     multiple of S; the caller zeroes the padding s >= S (dtk_vit_forward does), it is not written
  *   DTK_VIT_GEMM_QKV_FACET  3D x D    out_f32 [rows][3D] = A W^T + bias
- *   DTK_VIT_GEMM_PROJ       D x D     out [rows][D] = gamma * (A W^T + bias), 16-bit (the pending residual update)
+ *   DTK_VIT_GEMM_PROJ       D x D     out [rows][D] = gamma * (A W^T + bias), 16-bit (the pending residual update).  With ln_out set: as
+ *                                     FC2 below, where dtk_vit_forward fuses the block's LayerNorm-2 (D = 384, none of TILED_GEMMS /
+ *                                     GEMM_WS_V1 / GEMM_WIDE_V1 / NO_LN_FUSION)
  *   DTK_VIT_GEMM_FC1        4D x D    out [rows][4D] = GELU(A W^T + bias), 16-bit
  *   DTK_VIT_GEMM_FC2        D x 4D    as PROJ.  With ln_out set (D = 384, none of TILED_GEMMS / GEMM_WIDE_V1 / NO_LN_FUSION: where
  *                                     dtk_vit_forward fuses it) the update is NOT stored: ln_x [rows][D] += it and ln_out [rows][D] =

@@ -9,6 +9,7 @@ NAMES = {  # kernel function -> launch name used by bench.py (only kernels with 
     "attention_kernel": "vit_attention", "attention2_kernel": "vit_attention", "attention4_kernel": "vit_attention", "attention6_kernel": "vit_attention", "corr_peaks_kernel": "corr_peaks", "refine_corr_kernel": "refine_corr_generic", "refine_corr_dma_kernel": "refine_corr",
     "refine_head_kernel": "refine_head", "layernorm_kernel": "vit_layernorm", "rescore_kernel": "rescore",
     "patch_embed_split_kernel": "vit_patch_embed", "conv1_split_kernel": "dd_conv1", "gemm_wide_delta_kernel": "vit_gemm_fc2",
+    "gemm_ws_ln_kernel": "vit_gemm_proj",   # the attention projection + LayerNorm-2 (csrc/vit_gemm_ws_ln.h)
 }
 
 def function_name(kn):
