@@ -45,12 +45,15 @@ class VitModel(ctypes.Structure):
                 ("patch_w", c_void_p), ("patch_b", c_void_p),
                 ("cls_pos", c_void_p), ("pos", c_void_p), ("mean_std", c_void_p), ("layers", ctypes.POINTER(VitLayer)),
                 ("frame_batch", ctypes.c_int32), ("overflow", c_void_p),
-                ("tap_out", c_void_p), ("tap_mask", ctypes.c_uint64), ("tap_scale", ctypes.c_float)]
+                ("tap_out", c_void_p), ("tap_mask", ctypes.c_uint64), ("tap_scale", ctypes.c_float),
+                ("ffn", ctypes.c_int32), ("hidden", ctypes.c_int32)]
 
 
 VIT_TILED_GEMMS, VIT_BF16, VIT_CHECK_RANGE, VIT_GEMM_WS_V1, VIT_ATTENTION_V4, VIT_GEMM_WIDE_V1, VIT_NO_LN_FUSION = 1, 2, 4, 16, 32, 64, 128  # dtk_vit_model.flags (8 is retired)
 OPERAND_F16, OPERAND_BF16, OPERAND_ATTENTION_V4 = 0, 1, 0x2000
 VIT_GEMM_QKV, VIT_GEMM_QKV_FACET, VIT_GEMM_PROJ, VIT_GEMM_FC1, VIT_GEMM_FC2 = 0, 1, 2, 3, 4   # dtk_vit_gemm_args.role
+VIT_GEMM_FC1_SWIGLU, VIT_GEMM_FC2_SWIGLU = 5, 6   # ViT-g (D = 1536): the packed w12 GEMM with the SwiGLU epilogue, and w3
+VIT_FFN_GELU, VIT_FFN_SWIGLU = 0, 1               # dtk_vit_model.ffn
 
 
 class VitGemmArgs(ctypes.Structure):

@@ -1,10 +1,10 @@
 // vit.hip -- P1: DINOv2 ViT encoder as driven by VitExtractor (models/extractor.py:41-150, utils.py:33-72):
 // overlapping patch embedding (14x14, stride 7) of ImageNet-normalised frames + interpolated position encoding,
 // `depth` transformer blocks (LN -> QKV -> MHSA -> proj -> LayerScale -> +res; LN -> fc1 -> GELU -> fc2 -> LayerScale
-// -> +res), output = residual stream after the last requested block (no final norm), CLS included.
+// -> +res; ViT-g/14: LN -> w12 -> silu(gate) * value -> w3 instead, dtk_vit_model.ffn), output = residual stream after the last requested block (no final norm), CLS included.
 //
 //   patch_embed_kernel  exact fp32 implicit GEMM on the f32-input MFMA (K = 3*14*14 = 588), mean/std fused in the load
-//   layernorm_kernel    one wave per token, fp32 statistics, 16-bit output
+//   layernorm_kernel    one wave per token, fp32 statistics, 16-bit output; the row in NIT float4 per lane (D <= 1024: 4, D <= 1536: 6)
 //   gemm_tiled_kernel   (vit_gemm_tiled.h) C = A W^T on MFMA 16x16x32 (fp32 accumulate), 128x128 tiles, LDS double-buffered, with
 //                       fused epilogues: QKV split (Q pre-scaled by log2(e)/sqrt(d), V written transposed), GELU,
 //                       LayerScale + residual add into the fp32 stream.  The forms the blocks run on: vit_gemm_ws.h (K = 384,
@@ -211,7 +211,7 @@ __global__ __launch_bounds__(256) void patch_embed_split_kernel(const h4v* __res
 // ---------------------------------------------------------------------------------------------------------------
 // LayerNorm: fp32 row -> bf16 row (A operand of the next GEMM); one wave per token
 // ---------------------------------------------------------------------------------------------------------------
-template <typename T>
+template <typename T, int NIT = 4>
 __global__ __launch_bounds__(256) void layernorm_kernel(float* __restrict__ x, const T* __restrict__ delta,
                                                         const float* __restrict__ gam, const float* __restrict__ bet,
                                                         T* __restrict__ y, long long rows, int D, float eps,
@@ -224,13 +224,13 @@ __global__ __launch_bounds__(256) void layernorm_kernel(float* __restrict__ x, c
     if (row >= rows) return;
     const int lane = threadIdx.x & 63;
     float* p = x + row * D;
-    // the row stays in registers (D <= 1024: four float4 per lane); a pending residual update (the LayerScale'd output of
+    // the row stays in registers (NIT float4 per lane: four for D <= 1024, six for D <= 1536 -- launch_layernorm); a pending residual update (the LayerScale'd output of
     // the previous projection / MLP, written by the GEMM epilogue) is applied here: x += delta
-    float4 v[4];
+    float4 v[NIT];
     float s = 0.f;
     bool sat = false;
 #pragma unroll
-    for (int it = 0; it < 4; ++it) {
+    for (int it = 0; it < NIT; ++it) {
         const int c = lane * 4 + it * 256;
         if (c < D) {
             v[it] = *reinterpret_cast<const float4*>(p + c);
@@ -249,7 +249,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(float* __restrict__ x, c
     const float mean = wave_sum(s) / (float)D;
     float q = 0.f;
 #pragma unroll
-    for (int it = 0; it < 4; ++it) {
+    for (int it = 0; it < NIT; ++it) {
         if (lane * 4 + it * 256 < D) {
             const float a = v[it].x - mean, b = v[it].y - mean, cc = v[it].z - mean, d = v[it].w - mean;
             q += (a * a + b * b) + (cc * cc + d * d);
@@ -259,7 +259,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(float* __restrict__ x, c
     if (!y) return;  // final residual update only
     T* o = y + row * D;
 #pragma unroll
-    for (int it = 0; it < 4; ++it) {
+    for (int it = 0; it < NIT; ++it) {
         const int c = lane * 4 + it * 256;
         if (c < D) {
             const float4 g = *reinterpret_cast<const float4*>(gam + c), b = *reinterpret_cast<const float4*>(bet + c);
@@ -408,6 +408,30 @@ __global__ __launch_bounds__(256) void range_scan_kernel(const T* __restrict__ p
     if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(flag, bit);
 }
 
+// The LayerNorm launches of vit_run: the kernels keep a row in NIT float4 per lane -- four up to D = 1024 (the code of ViT-S / B / L,
+// unchanged), six for D = 1536 (ViT-g); dtk_vit_forward refuses wider models.
+constexpr int VIT_MAX_D = 1536;
+template <typename T>
+int launch_layernorm(float* x, const T* delta, const float* gam, const float* bet, T* y, long long rows, int D, float eps, int* ovf,
+                     hipStream_t st) {
+    if (D <= 1024)
+        DTK_LAUNCH("vit_layernorm", (layernorm_kernel<T, 4>), dim3(dtk_cdiv(rows, 4)), dim3(256), 0, st, x, delta, gam, bet, y, rows, D, eps, ovf);
+    else
+        DTK_LAUNCH("vit_layernorm", (layernorm_kernel<T, 6>), dim3(dtk_cdiv(rows, 4)), dim3(256), 0, st, x, delta, gam, bet, y, rows, D, eps, ovf);
+    return DTK_OK;
+}
+template <typename T>
+int launch_layernorm_split(float* x, const T* delta, const float* gam, const float* bet, T* y_hi, T* y_lo, long long rows, int D,
+                           float eps, int* ovf, hipStream_t st) {
+    if (D <= 1024)
+        DTK_LAUNCH("vit_layernorm_split", (layernorm_split_kernel<T, 4>), dim3(dtk_cdiv(rows, 4)), dim3(256), 0, st, x, delta, gam, bet, y_hi,
+                   y_lo, rows, D, eps, ovf);
+    else
+        DTK_LAUNCH("vit_layernorm_split", (layernorm_split_kernel<T, 6>), dim3(dtk_cdiv(rows, 4)), dim3(256), 0, st, x, delta, gam, bet, y_hi,
+                   y_lo, rows, D, eps, ovf);
+    return DTK_OK;
+}
+
 // Which kernels the GEMMs of a pass run on: decided once from the model width D and dtk_vit_model.flags (NOT from a GEMM's own K).
 struct GemmPath {
     bool tiled;    // DTK_VIT_TILED_GEMMS: every GEMM on the register-staged 128 x 128 kernels (the tests' cross-check)
@@ -436,6 +460,7 @@ inline GemmPath gemm_path(const dtk_vit_model* m) { return gemm_path(m->D, m->fl
 //                                                                          e.ln_out set: <T, true, true>)
 //   path.wide                           gemm_wide_kernel<T, EPI>          (wide_v1: <T, EPI, false>)     gemm_wide_grid(N)   x 512
 //   otherwise                           gemm_tiled_kernel<T, EPI>                                        gemm_grid(N)        x 256
+// (EPI_SWIGLU, the w12 GEMM of ViT-g, has its own two-line launcher below: launch_gemm_swiglu.)
 //
 // (path.ws and path.wide exclude each other: 384 is not a multiple of 256.  The caller sets e.ln_* only under path.fc2_ln (fc2) /
 //  path.proj_ln (proj).)
@@ -488,6 +513,24 @@ int launch_gemm(const char* name, const GemmPath& path, const T* A, const T* W, 
     return DTK_OK;
 }
 
+// The w12 GEMM of a SwiGLU block (ViT-g: D = 1536, N = 2 x 4096 packed rows, EPI_SWIGLU): gemm_wide_kernel<T, EPI_SWIGLU> (path.wide:
+// 1536 is a multiple of 256) or, DTK_VIT_TILED_GEMMS, gemm_tiled_kernel<T, EPI_SWIGLU>.  There is no *_V1 form: vit_swiglu_flags_ok.
+template <typename T>
+int launch_gemm_swiglu(const char* name, const GemmPath& path, const T* A, const T* W, long long rows, int N, int K, const GemmEpi<T>& e,
+                       hipStream_t st) {
+    if (path.wide)
+        DTK_LAUNCH(name, (gemm_wide_kernel<T, EPI_SWIGLU, true>), dim3(gemm_wide_grid(N, rows)), dim3(512), 0, st, A, W, rows, N, K, e);
+    else
+        DTK_LAUNCH(name, (gemm_tiled_kernel<T, EPI_SWIGLU>), dim3(gemm_grid(N, rows)), dim3(256), 0, st, A, W, rows, N, K, e);
+    return DTK_OK;
+}
+inline bool vit_swiglu_flags_ok(int flags, const char* who) {
+    if (!(flags & (DTK_VIT_GEMM_WIDE_V1 | DTK_VIT_GEMM_WS_V1))) return true;
+    dtk_set_error("%s: the SwiGLU feed-forward has no A / B kernel forms: clear %s", who,
+                  (flags & DTK_VIT_GEMM_WIDE_V1) ? "DTK_VIT_GEMM_WIDE_V1" : "DTK_VIT_GEMM_WS_V1");
+    return false;
+}
+
 // One GEMM of a split block (vit_split.h), every SEPI.  (The LDS-DMA form, round 6: fc2 38.3 -> 34.5, qkv 41.4 -> 39.3 ms per step, ViT-L
 // 1613 -> 1461 ms.)
 //   !path.tiled and N % 128 == 0        gemm_split_dma_kernel<T, SEPI, true>   (wide_v1: <T, SEPI, false>)   gemm_split_dma_grid(N) x 512
@@ -497,7 +540,9 @@ int launch_gemm_split(const char* name, const GemmPath& path, const T* Ah, const
                       int N, int K, const SplitEpi<T>& se, hipStream_t st) {
     if (!path.tiled && N % SD_N == 0) {
         const dim3 grid(gemm_split_dma_grid(N, rows));
-        if (path.wide_v1)
+        if constexpr (SEPI == SEPI_SWIGLU)   // (staged only; the flag is refused for such a model)
+            DTK_LAUNCH(name, (gemm_split_dma_kernel<T, SEPI, true>), grid, dim3(512), 0, st, Ah, Al, Wh, Wl, rows, N, K, se);
+        else if (path.wide_v1)
             DTK_LAUNCH(name, (gemm_split_dma_kernel<T, SEPI, false>), grid, dim3(512), 0, st, Ah, Al, Wh, Wl, rows, N, K, se);
         else
             DTK_LAUNCH(name, (gemm_split_dma_kernel<T, SEPI, true>), grid, dim3(512), 0, st, Ah, Al, Wh, Wl, rows, N, K, se);
@@ -511,6 +556,10 @@ template <typename T>
 int vit_run(const dtk_vit_model* m, const float* frames, int nframes, int video_h, int video_w, float* tokens_out,
             float* feat_out, float* qkv_out, unsigned char* ws, const VitPlan& p, int ph, int pw, hipStream_t st) {
     const int HW = ph * pw, D = m->D;
+    // the feed-forward: GELU MLP (hidden 4 D) or, ViT-g, SwiGLU -- fc1_w is then the PACKED w12 [2 hidden][D] (include/dtk.h) and the
+    // GEMM's epilogue writes silu(gate) * value, fc2_w is w3 [D][hidden]; `hid` is sized for 4 D >= hidden
+    const bool swiglu = m->ffn == DTK_VIT_FFN_SWIGLU;
+    const int HID = m->hidden > 0 ? m->hidden : 4 * D;
     float* x = reinterpret_cast<float*>(ws + p.x);
     auto at = [&](size_t off) { return reinterpret_cast<T*>(ws + off); };
     T *xn = at(p.xn), *q = at(p.q), *k = at(p.k), *vt = at(p.vt), *ao = at(p.ao), *hid = at(p.hid), *delta = at(p.delta);
@@ -591,8 +640,8 @@ int vit_run(const dtk_vit_model* m, const float* frames, int nframes, int video_
                 const T* fc1_wl = reinterpret_cast<const T*>(L.fc1_w_lo);
                 const T* fc2_wl = reinterpret_cast<const T*>(L.fc2_w_lo);
                 const float inv_ws = 1.f / (L.w_scale > 0.f ? L.w_scale : 1.f);
-                DTK_LAUNCH("vit_layernorm_split", layernorm_split_kernel<T>, dim3(dtk_cdiv(rows, 4)), dim3(256), 0, st, x,
-                           pending ? (const T*)delta : (const T*)nullptr, L.ln1_w, L.ln1_b, xn, xn_lo, rows, D, m->ln_eps, ovf);
+                if (launch_layernorm_split<T>(x, pending ? (const T*)delta : (const T*)nullptr, L.ln1_w, L.ln1_b, xn, xn_lo, rows, D, m->ln_eps,
+                                              ovf, st)) return DTK_E_HIP;
                 pending = false;
                 SplitEpi<T> se{};
                 if (qkv_out && l == m->depth - 1) {
@@ -611,21 +660,20 @@ int vit_run(const dtk_vit_model* m, const float* frames, int nframes, int video_
                 se = SplitEpi<T>{};
                 se.bias = L.proj_b; se.inv_wscale = inv_ws; se.x = x; se.gamma = L.ls1;
                 if (launch_gemm_split<T, SEPI_RESID>("vit_gemm_proj_split", path, ao, ao_lo, proj_w, proj_wl, rows, D, D, se, st)) return DTK_E_HIP;
-                DTK_LAUNCH("vit_layernorm_split", layernorm_split_kernel<T>, dim3(dtk_cdiv(rows, 4)), dim3(256), 0, st, x,
-                           (const T*)nullptr, L.ln2_w, L.ln2_b, xn, xn_lo, rows, D, m->ln_eps, ovf);
+                if (launch_layernorm_split<T>(x, (const T*)nullptr, L.ln2_w, L.ln2_b, xn, xn_lo, rows, D, m->ln_eps, ovf, st)) return DTK_E_HIP;
                 se = SplitEpi<T>{};
                 se.bias = L.fc1_b; se.inv_wscale = inv_ws; se.out_hi = hid; se.out_lo = hid_lo; se.ovf = epi_ovf;
-                if (launch_gemm_split<T, SEPI_GELU>("vit_gemm_fc1_split", path, xn, xn_lo, fc1_w, fc1_wl, rows, 4 * D, D, se, st)) return DTK_E_HIP;
+                if (swiglu ? launch_gemm_split<T, SEPI_SWIGLU>("vit_gemm_fc1_split", path, xn, xn_lo, fc1_w, fc1_wl, rows, 2 * HID, D, se, st)
+                           : launch_gemm_split<T, SEPI_GELU>("vit_gemm_fc1_split", path, xn, xn_lo, fc1_w, fc1_wl, rows, HID, D, se, st)) return DTK_E_HIP;
                 se = SplitEpi<T>{};
                 se.bias = L.fc2_b; se.inv_wscale = inv_ws; se.x = x; se.gamma = L.ls2;
-                if (launch_gemm_split<T, SEPI_RESID>("vit_gemm_fc2_split", path, hid, hid_lo, fc2_w, fc2_wl, rows, D, 4 * D, se, st)) return DTK_E_HIP;
+                if (launch_gemm_split<T, SEPI_RESID>("vit_gemm_fc2_split", path, hid, hid_lo, fc2_w, fc2_wl, rows, D, HID, se, st)) return DTK_E_HIP;
                 if (tap(l, false)) return DTK_E_HIP;
                 continue;
             }
             GemmEpi<T> e{};
-            if (!ln1_done)
-                DTK_LAUNCH("vit_layernorm", layernorm_kernel<T>, dim3(dtk_cdiv(rows, 4)), dim3(256), 0, st, x,
-                           pending ? (const T*)delta : (const T*)nullptr, L.ln1_w, L.ln1_b, xn, rows, D, m->ln_eps, ovf);
+            if (!ln1_done && launch_layernorm<T>(x, pending ? (const T*)delta : (const T*)nullptr, L.ln1_w, L.ln1_b, xn, rows, D, m->ln_eps, ovf, st))
+                return DTK_E_HIP;
             ln1_done = false;
             pending = true;
             if (qkv_out && l == m->depth - 1) {  // the qkv hook of the reference (models/extractor.py:107-118), fp32 out
@@ -644,13 +692,12 @@ int vit_run(const dtk_vit_model* m, const float* frames, int nframes, int video_
             // not stored) -- `pending` / `ln1_done` speak of fc2's update and LayerNorm-1 only, and stay as they are
             if (path.proj_ln) { e.ln_x = x; e.ln_w = L.ln2_w; e.ln_b = L.ln2_b; e.ln_out = xn; e.ln_eps = m->ln_eps; e.ln_ovf = ovf; }
             if (launch_gemm<T, EPI_DELTA>("vit_gemm_proj", path, ao, proj_w, rows, D, D, e, st)) return DTK_E_HIP;
-            if (!path.proj_ln)
-                DTK_LAUNCH("vit_layernorm", layernorm_kernel<T>, dim3(dtk_cdiv(rows, 4)), dim3(256), 0, st, x, (const T*)delta,
-                           L.ln2_w, L.ln2_b, xn, rows, D, m->ln_eps, ovf);
+            if (!path.proj_ln && launch_layernorm<T>(x, (const T*)delta, L.ln2_w, L.ln2_b, xn, rows, D, m->ln_eps, ovf, st)) return DTK_E_HIP;
             e = GemmEpi<T>{};
             e.bias = L.fc1_b; e.out = hid; e.no_store = dbg_ns; e.ovf = epi_ovf;
-            if (launch_gemm<T, EPI_GELU>("vit_gemm_fc1", path, xn, fc1_w, rows, 4 * D, D, e, st)) return DTK_E_HIP;
-            if (scan_all && scan_range(hid, rows * 4 * D, 4)) return DTK_E_HIP;
+            if (swiglu ? launch_gemm_swiglu<T>("vit_gemm_fc1", path, xn, fc1_w, rows, 2 * HID, D, e, st)
+                       : launch_gemm<T, EPI_GELU>("vit_gemm_fc1", path, xn, fc1_w, rows, HID, D, e, st)) return DTK_E_HIP;
+            if (scan_all && scan_range(hid, rows * HID, 4)) return DTK_E_HIP;
             e = GemmEpi<T>{};
             e.bias = L.fc2_b; e.delta = delta; e.gamma = L.ls2; e.no_store = dbg_ns;
             // round 6: the LayerNorm of the next block runs inside fc2's epilogue when that block is a fast one (the split blocks
@@ -661,7 +708,7 @@ int vit_run(const dtk_vit_model* m, const float* frames, int nframes, int video_
                 pending = false;      // x is up to date ...
                 ln1_done = true;      // ... and xn holds the next block's normalised rows
             }
-            if (launch_gemm<T, EPI_DELTA>("vit_gemm_fc2", path, hid, fc2_w, rows, D, 4 * D, e, st)) return DTK_E_HIP;
+            if (launch_gemm<T, EPI_DELTA>("vit_gemm_fc2", path, hid, fc2_w, rows, D, HID, e, st)) return DTK_E_HIP;
             if (tap(l, pending)) return DTK_E_HIP;
         }
         if (pending && (tokens_out || feat_out)) {
@@ -671,9 +718,9 @@ int vit_run(const dtk_vit_model* m, const float* frames, int nframes, int video_
                        tokens_out ? tokens_out + (size_t)f0 * S * D : (float*)nullptr,
                        feat_out ? feat_out + (size_t)f0 * HW * D : (float*)nullptr, S, D, t4, ovf);
         } else {   // depth 0 (embedding + position encoding only) or a split last block: no pending update
-            if (pending)   // (qkv_out only: keep the residual-update check of the last block)
-                DTK_LAUNCH("vit_layernorm", layernorm_kernel<T>, dim3(dtk_cdiv(rows, 4)), dim3(256), 0, st, x, (const T*)delta,
-                           (const float*)nullptr, (const float*)nullptr, (T*)nullptr, rows, D, m->ln_eps, ovf);
+            if (pending &&   // (qkv_out only: keep the residual-update check of the last block)
+                launch_layernorm<T>(x, (const T*)delta, (const float*)nullptr, (const float*)nullptr, (T*)nullptr, rows, D, m->ln_eps, ovf, st))
+                return DTK_E_HIP;
             if (tokens_out)
                 DTK_HIP(hipMemcpyAsync(tokens_out + (size_t)f0 * S * D, x, (size_t)rows * D * sizeof(float),
                                        hipMemcpyDeviceToDevice, st));
@@ -690,9 +737,10 @@ int vit_run(const dtk_vit_model* m, const float* frames, int nframes, int video_
 // ---- one GEMM of a block on its own (dtk_vit_gemm / dtk_vit_gemm_split) ------------------------------------------------------------
 // The role names the shape and the epilogue; the kernel is what launch_gemm / launch_gemm_split choose for a model of width D with
 // these flags (gemm_path: the dispatch of vit_run, no second table), under the launch names of vit_run.
+constexpr int VITG_HIDDEN = 4096;   // upstream vit_giant2: (int(4 * 1536 * 2 / 3) + 7) / 8 * 8
 int vit_gemm_check(const dtk_vit_gemm_args* g, const char* who, bool split, int* N, int* K) {
     DTK_REQUIRE(g, "%s: null pointer", who);
-    DTK_REQUIRE(g->D == 384 || g->D == 768 || g->D == 1024, "%s: D must be 384, 768 or 1024 (got %d)", who, g->D);
+    DTK_REQUIRE(g->D == 384 || g->D == 768 || g->D == 1024 || g->D == 1536, "%s: D must be 384, 768 or 1024, or ViT-g's 1536 (got %d)", who, g->D);
     DTK_REQUIRE(g->operand_type == DTK_OPERAND_F16 || g->operand_type == DTK_OPERAND_BF16, "%s: operand_type", who);
     DTK_REQUIRE(g->rows > 0 && g->rows < (1ll << 31), "%s: rows", who);
     DTK_REQUIRE(g->a && g->w && (!split || (g->a_lo && g->w_lo)), "%s: null operand", who);
@@ -716,6 +764,18 @@ int vit_gemm_check(const dtk_vit_gemm_args* g, const char* who, bool split, int*
         case DTK_VIT_GEMM_FC2:
             *N = D; *K = g->role == DTK_VIT_GEMM_FC2 ? 4 * D : D;
             DTK_REQUIRE(g->gamma && (split ? g->x != nullptr : g->out != nullptr), "%s: PROJ / FC2 need gamma and %s", who, split ? "x" : "out");
+            break;
+        case DTK_VIT_GEMM_FC1_SWIGLU:
+        case DTK_VIT_GEMM_FC2_SWIGLU:
+            DTK_REQUIRE(D == 1536, "%s: the SwiGLU roles are ViT-g's, D = 1536 (got %d)", who, D);
+            if (!vit_swiglu_flags_ok(g->flags, who)) return DTK_E_INVALID;
+            if (g->role == DTK_VIT_GEMM_FC1_SWIGLU) {
+                *N = 2 * VITG_HIDDEN; *K = D;
+                DTK_REQUIRE(g->out && (!split || g->out_lo), "%s: FC1_SWIGLU needs out", who);
+            } else {
+                *N = D; *K = VITG_HIDDEN;
+                DTK_REQUIRE(g->gamma && (split ? g->x != nullptr : g->out != nullptr), "%s: FC2_SWIGLU needs gamma and %s", who, split ? "x" : "out");
+            }
             break;
         default:
             DTK_REQUIRE(false, "%s: unknown role %d", who, g->role);
@@ -741,10 +801,13 @@ int vit_gemm_stage(const dtk_vit_gemm_args* g, int N, int K, hipStream_t st) {
         case DTK_VIT_GEMM_FC1:
             e.out = reinterpret_cast<T*>(g->out); e.ovf = epi_ovf;
             return launch_gemm<T, EPI_GELU>("vit_gemm_fc1", path, A, W, g->rows, N, K, e, st);
+        case DTK_VIT_GEMM_FC1_SWIGLU:
+            e.out = reinterpret_cast<T*>(g->out); e.ovf = epi_ovf;
+            return launch_gemm_swiglu<T>("vit_gemm_fc1", path, A, W, g->rows, N, K, e, st);
         default:
             e.delta = reinterpret_cast<T*>(g->out); e.gamma = g->gamma;
             if (g->ln_out) {   // the LayerNorm inside fc2's (the next block's) or the projection's (LayerNorm-2) epilogue: where vit_run fuses it, nowhere else
-                DTK_REQUIRE(g->role == DTK_VIT_GEMM_FC2 ? path.fc2_ln : path.proj_ln,
+                DTK_REQUIRE(g->role == DTK_VIT_GEMM_PROJ ? path.proj_ln : path.fc2_ln,
                             "dtk_vit_gemm: the fused LayerNorm is fc2's or the projection's at D = 384 without TILED_GEMMS / GEMM_WIDE_V1 / NO_LN_FUSION (the projection's: nor GEMM_WS_V1)");
                 DTK_REQUIRE(g->ln_x && g->ln_w && g->ln_b, "dtk_vit_gemm: the fused LayerNorm needs ln_x, ln_w and ln_b");
                 e.ln_x = g->ln_x; e.ln_w = g->ln_w; e.ln_b = g->ln_b; e.ln_out = reinterpret_cast<T*>(g->ln_out); e.ln_eps = g->ln_eps;
@@ -774,6 +837,9 @@ int vit_gemm_split_stage(const dtk_vit_gemm_args* g, int N, int K, hipStream_t s
         case DTK_VIT_GEMM_FC1:
             se.out_hi = reinterpret_cast<T*>(g->out); se.out_lo = reinterpret_cast<T*>(g->out_lo); se.ovf = epi_ovf;
             return launch_gemm_split<T, SEPI_GELU>("vit_gemm_fc1_split", path, Ah, Al, Wh, Wl, g->rows, N, K, se, st);
+        case DTK_VIT_GEMM_FC1_SWIGLU:
+            se.out_hi = reinterpret_cast<T*>(g->out); se.out_lo = reinterpret_cast<T*>(g->out_lo); se.ovf = epi_ovf;
+            return launch_gemm_split<T, SEPI_SWIGLU>("vit_gemm_fc1_split", path, Ah, Al, Wh, Wl, g->rows, N, K, se, st);
         default:
             se.x = g->x; se.gamma = g->gamma;
             return launch_gemm_split<T, SEPI_RESID>(g->role == DTK_VIT_GEMM_PROJ ? "vit_gemm_proj_split" : "vit_gemm_fc2_split", path, Ah, Al,
@@ -803,6 +869,15 @@ extern "C" int dtk_vit_forward(const dtk_vit_model* m, const float* frames, int 
     DTK_REQUIRE(m->D > 0 && m->heads > 0 && m->D == m->heads * 64, "dtk_vit_forward: d_head must be 64 (D=%d heads=%d)",
                 m->D, m->heads);
     DTK_REQUIRE(m->D % 32 == 0 && m->depth >= 0 && m->layers, "dtk_vit_forward: bad model");
+    DTK_REQUIRE(m->D <= VIT_MAX_D, "dtk_vit_forward: D = %d: the LayerNorm kernels hold rows of at most %d channels", m->D, VIT_MAX_D);
+    if (m->ffn == DTK_VIT_FFN_SWIGLU) {
+        DTK_REQUIRE(m->D == 1536 && m->hidden == VITG_HIDDEN, "dtk_vit_forward: the SwiGLU feed-forward is ViT-g's: D = 1536, hidden = %d (got D = %d, hidden = %d)",
+                    VITG_HIDDEN, m->D, m->hidden);
+        if (!vit_swiglu_flags_ok(m->flags, "dtk_vit_forward")) return DTK_E_INVALID;
+    } else {
+        DTK_REQUIRE(m->ffn == DTK_VIT_FFN_GELU, "dtk_vit_forward: unknown ffn %d", m->ffn);
+        DTK_REQUIRE(m->hidden == 0 || m->hidden == 4 * m->D, "dtk_vit_forward: a GELU MLP has hidden = 4 D (got %d)", m->hidden);
+    }
     DTK_REQUIRE(video_h >= m->patch && video_w >= m->patch, "dtk_vit_forward: frame smaller than a patch");
     const int ph = 1 + (video_h - m->patch) / m->stride, pw = 1 + (video_w - m->patch) / m->stride;
     const VitPlan p = vit_plan(m, ph, pw, nframes);

@@ -34,7 +34,7 @@ template <typename T> __device__ __forceinline__ void operand_mode() {
 // bf16 GEMM  C[M][N] = A[M][K] . Wt[N][K]^T (+bias) with fused epilogues
 // ---------------------------------------------------------------------------------------------------------------
 constexpr int GM = 128, GN = 128, GK = 32;
-enum { EPI_QKV = 0, EPI_GELU = 1, EPI_DELTA = 2, EPI_F32 = 3 };
+enum { EPI_QKV = 0, EPI_GELU = 1, EPI_DELTA = 2, EPI_F32 = 3, EPI_SWIGLU = 4 };
 
 template <typename T>
 struct GemmEpi {
@@ -45,7 +45,7 @@ struct GemmEpi {
     T* vt;          // [F][heads][64][Sp]
     int S, Sp, heads, D;
     float qscale;
-    // EPI_GELU
+    // EPI_GELU; EPI_SWIGLU: [M][N / 2] (the packed w12 rows, see swiglu_col)
     T* out;         // [M][N]
     // EPI_DELTA
     int no_store;        // DTK_DEV builds: DTK_DEBUG >> 16 -- 1 | 2: skip the stores of the weight-stationary kernel; 4 .. 16: the wide kernels;
@@ -72,11 +72,33 @@ struct GemmEpi {
 __device__ __forceinline__ float amax2(float m, float a, float b) { return fmaxf(fmaxf(m, fabsf(a)), fabsf(b)); }
 template <typename T, int EPI>
 __device__ __forceinline__ void amax_report(float amax, int* ovf) {
-    if (IsF16<T>::value && (EPI == EPI_QKV || EPI == EPI_GELU) && ovf) {
+    if (IsF16<T>::value && (EPI == EPI_QKV || EPI == EPI_GELU || EPI == EPI_SWIGLU) && ovf) {
         // (65488 = the midpoint below 65504: an fp32 value from there on is STORED as 65504, which the explicit scan of the tensor
         //  -- DTK_VIT_CHECK_RANGE -- reports)
         if (__any(amax >= 65488.f) && (threadIdx.x & 63) == 0) atomicOr(ovf, EPI == EPI_QKV ? 2 : 4);
     }
+}
+
+// SwiGLU feed-forward of ViT-g (upstream SwiGLUFFNFused): hidden[j] = silu(pre[j]) * pre[H + j], pre = A w12^T + b12, H = 4096.  The
+// rows of w12 / b12 are PACKED on the host (include/dtk.h, dtk_vit_model.ffn) so that every aligned group of 64 packed columns is 32 gate
+// columns followed by their 32 value columns: in all four GEMM forms a wave owns 64 consecutive columns as four 16-wide MFMA fragments
+// ni = 0 .. 3, so gate (ni = 0, 1) and value (ni + 2) of a pair are accumulators of the SAME lane and the product costs no second pass.
+// Packed column n of a gate fragment -> hidden column:
+__device__ __forceinline__ int swiglu_col(int n) { return ((n >> 6) << 5) + (n & 31); }
+// silu(v) = v / (1 + exp(-v)) in fp32 from the accumulator: exp through v_exp_f32 (1 ulp) on -v log2(e), the quotient through v_rcp_f32
+// (1 ulp).  Finite for every finite v: exp(-v) = +inf for v < -88.8 gives v * 0 = -0, exp(-v) = 0 for large v gives v.
+// SILU_ERR: |silu~(v) - silu(v)| <= 4e-7 * max(1, |v|)  (five roundings of <= 1 ulp on a result of magnitude <= |v|, and the argument's
+// rounding |v| 2^-24 acting on exp only where silu is small; an fp32 emulation measures 1.8e-7 over [-100, 100] and at +-1e4:
+// tests/test_vitg_reference.py).
+__device__ __forceinline__ float silu_f32(float v) {
+    const float e = __builtin_amdgcn_exp2f(v * -1.4426950408889634f);
+    return v * __builtin_amdgcn_rcpf(1.f + e);
+}
+// one pair: what is stored (before the rounding to T), and its |.| into the running maximum of the fp16 range check
+__device__ __forceinline__ float swiglu_pair(float gate, float value, float& amax) {
+    const float h = silu_f32(gate) * value;
+    amax = fmaxf(amax, fabsf(h));
+    return h;
 }
 
 // LDS image of an operand tile: row-major, four 16-byte pieces per row, piece p of row r in slot p ^ gswz_f(r)
@@ -148,6 +170,19 @@ __device__ __forceinline__ void gemm_store_tile(const f4& a, long long mb, int n
             const long long m = mb + r;
             if (m < M) e.delta[m * N + n] = (T)(gm * (a[r] + bias));
         }
+    }
+}
+
+// EPI_SWIGLU on the tiled kernel: gate tile `a` (packed column n, bias bg) and value tile `b` (packed column n + 32, bias bv) of rows
+// mb .. mb + 3 -> out[m][swiglu_col(n)], N = the PACKED width
+template <typename T>
+__device__ __forceinline__ void gemm_store_tile_swiglu(const f4& a, const f4& b, long long mb, int n, float bg, float bv, long long M,
+                                                       int N, const GemmEpi<T>& e, float& amax) {
+    const int hc = swiglu_col(n), NH = N >> 1;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const float h = swiglu_pair(a[r] + bg, b[r] + bv, amax);   // rows past M hold the repeated last row: harmless
+        if (mb + r < M) e.out[(mb + r) * NH + hc] = (T)h;
     }
 }
 

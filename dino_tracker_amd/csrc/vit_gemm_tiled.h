@@ -88,6 +88,18 @@ __global__ __launch_bounds__(256) void gemm_tiled_kernel(const T* __restrict__ A
     }
     // D fragment: lane (fg, fj) holds rows 4*fg + r (r = 0..3), column fj of each 16x16 tile
     float amax = 0.f;
+    if constexpr (EPI == EPI_SWIGLU) {   // (N = 8192: whole tiles) gate fragments ni = 0, 1 with their value fragments ni + 2
+#pragma unroll
+        for (int ni = 0; ni < 2; ++ni) {
+            const int n = n0 + wc * 64 + ni * 16 + fj;
+            const float bg = e.bias ? e.bias[n] : 0.f, bv = e.bias ? e.bias[n + 32] : 0.f;
+#pragma unroll
+            for (int mi = 0; mi < 4; ++mi)
+                gemm_store_tile_swiglu<T>(acc[mi][ni], acc[mi][ni + 2], m0 + wr * 64 + mi * 16 + fg * 4, n, bg, bv, M, N, e, amax);
+        }
+        amax_report<T, EPI>(amax, e.ovf);
+        return;
+    }
 #pragma unroll
     for (int ni = 0; ni < 4; ++ni) {
         const int n = n0 + wc * 64 + ni * 16 + fj;

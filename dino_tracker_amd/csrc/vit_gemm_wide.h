@@ -376,7 +376,38 @@ __global__ __launch_bounds__(512, 2) void gemm_wide_kernel(const T* __restrict__
     dtk_vm_wait<0>();
     // D tiles are TRANSPOSED (the MFMAs above multiply (W tile) x (token tile)^T): lane (fg, fj) holds features 4 fg + r of token fj
     float amax = 0.f;
-    if (PIPE && EPI != EPI_QKV) {
+    if constexpr (EPI == EPI_SWIGLU) {
+        // The w12 GEMM of ViT-g (vit_gemm_common.h, swiglu_col): a wave's 64 packed columns are 32 gate columns (fragments ni = 0, 1) and
+        // their 32 value columns (ni + 2) -- silu(gate) * value from the lane's own accumulators, staged as the 256 x 128 HIDDEN tile
+        // (row pitch 264 B: the 8-byte writes of 16 tokens fall on 16 different bank pairs, as with W2_OPITCH) and written as whole
+        // 256-byte rows of out [M][N / 2], 16 bytes per lane, four rows per wave and instruction.
+        static_assert(PIPE, "EPI_SWIGLU has no direct-store form");
+        constexpr int HP = W2_N + 8;   // staged hidden rows: 128 values x 2 B + 8
+        static_assert(W2_M * HP <= W2_LDS_BYTES, "the staged hidden tile must fit");
+        __syncthreads();   // every wave's requests have landed (the wait above) and every wave is done with the stages
+#pragma unroll
+        for (int ni = 0; ni < 2; ++ni) {
+            const int cb = wc * 64 + ni * 16 + fg * 4, hb = wc * 32 + ni * 16 + fg * 4;
+            const float4 bg = e.bias ? *reinterpret_cast<const float4*>(e.bias + n0 + cb) : make_float4(0.f, 0.f, 0.f, 0.f);
+            const float4 bv = e.bias ? *reinterpret_cast<const float4*>(e.bias + n0 + cb + 32) : make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+            for (int mi = 0; mi < 8; ++mi) {
+                const f4 &g = acc[mi][ni], &v = acc[mi][ni + 2];
+                const float h0 = swiglu_pair(g[0] + bg.x, v[0] + bv.x, amax), h1 = swiglu_pair(g[1] + bg.y, v[1] + bv.y, amax);
+                const float h2 = swiglu_pair(g[2] + bg.z, v[2] + bv.z, amax), h3 = swiglu_pair(g[3] + bg.w, v[3] + bv.w, amax);
+                *reinterpret_cast<T4*>(stages + (wr * 128 + mi * 16 + fj) * HP + hb * 2) = T4{(T)h0, (T)h1, (T)h2, (T)h3};
+            }
+        }
+        __syncthreads();
+        const int NH = N >> 1;
+        T* const outp = e.out + (n0 >> 1) + (tid & 15) * 8;
+#pragma unroll 4
+        for (int it = 0; it < W2_M / 32; ++it) {
+            const int row = it * 32 + (tid >> 4);
+            const uint4 v = staged16(stages + row * HP + (tid & 15) * 16);
+            if (m0 + row < M && !DTK_DBG(e.no_store, 4)) *reinterpret_cast<uint4*>(outp + (m0 + row) * NH) = v;
+        }
+    } else if (PIPE && EPI != EPI_QKV) {
         // Round 6: the [M][N] epilogues leave through LDS.  A store instruction of the direct form below covers 16 tokens x 32 bytes --
         // sixteen quarter lines; with everything but the epilogue switched off (DTK_DEV ablation) the stores of fc1 at D = 1024 ran at
         // 1.5 TB/s and cost a third of the kernel, because a CU holds ONE workgroup of this kernel (128 KB of stages) and nothing

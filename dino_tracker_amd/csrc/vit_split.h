@@ -29,7 +29,7 @@
 namespace {
 
 constexpr int SP_M = 128, SP_N = 128, SP_K = 32;
-enum { SEPI_QKV = 0, SEPI_GELU = 1, SEPI_RESID = 2, SEPI_F32 = 3 };
+enum { SEPI_QKV = 0, SEPI_GELU = 1, SEPI_RESID = 2, SEPI_F32 = 3, SEPI_SWIGLU = 4 };
 
 template <typename T>
 struct SplitEpi {
@@ -39,7 +39,7 @@ struct SplitEpi {
     T *q_hi, *q_lo, *k_hi, *k_lo, *vt_hi, *vt_lo;   // [F][heads][Sp][64] / [F][heads][64][Sp]
     int S, Sp, heads, D;
     float qscale;
-    // SEPI_GELU
+    // SEPI_GELU; SEPI_SWIGLU: [M][N / 2] (packed w12 rows: vit_gemm_common.h, swiglu_col)
     T *out_hi, *out_lo;    // [M][N]
     // SEPI_RESID: x[m][n] += gamma[n] * (acc + bias[n])   (fp32 residual stream, read-modify-write by the lane that owns it)
     float* x;
@@ -69,7 +69,7 @@ __device__ __forceinline__ float gelu_erfc(float x) {
 }
 
 // ---- LayerNorm -> hi / lo planes ------------------------------------------------------------------------------------------
-template <typename T>
+template <typename T, int NIT = 4>   // NIT float4 of the row per lane: vit.hip, launch_layernorm_split
 __global__ __launch_bounds__(256) void layernorm_split_kernel(float* __restrict__ x, const T* __restrict__ delta,
                                                               const float* __restrict__ gam, const float* __restrict__ bet,
                                                               T* __restrict__ y_hi, T* __restrict__ y_lo, long long rows, int D,
@@ -80,11 +80,11 @@ __global__ __launch_bounds__(256) void layernorm_split_kernel(float* __restrict_
     if (row >= rows) return;
     const int lane = threadIdx.x & 63;
     float* p = x + row * D;
-    float4 v[4];
+    float4 v[NIT];
     float s = 0.f;
     bool sat = false;
 #pragma unroll
-    for (int it = 0; it < 4; ++it) {
+    for (int it = 0; it < NIT; ++it) {
         const int c = lane * 4 + it * 256;
         if (c < D) {
             v[it] = *reinterpret_cast<const float4*>(p + c);
@@ -102,7 +102,7 @@ __global__ __launch_bounds__(256) void layernorm_split_kernel(float* __restrict_
     const float mean = wave_sum(s) / (float)D;
     float q = 0.f;
 #pragma unroll
-    for (int it = 0; it < 4; ++it) {
+    for (int it = 0; it < NIT; ++it) {
         if (lane * 4 + it * 256 < D) {
             const float a = v[it].x - mean, b = v[it].y - mean, cc = v[it].z - mean, d = v[it].w - mean;
             q += (a * a + b * b) + (cc * cc + d * d);
@@ -110,7 +110,7 @@ __global__ __launch_bounds__(256) void layernorm_split_kernel(float* __restrict_
     }
     const float rstd = rsqrtf(wave_sum(q) / (float)D + eps);
 #pragma unroll
-    for (int it = 0; it < 4; ++it) {
+    for (int it = 0; it < NIT; ++it) {
         const int c = lane * 4 + it * 256;
         if (c < D) {
             const float4 g = *reinterpret_cast<const float4*>(gam + c), b = *reinterpret_cast<const float4*>(bet + c);
@@ -180,6 +180,32 @@ __device__ __forceinline__ void split_store_tile(const f4& a, long long m, int n
         if (m >= M) return;
         *reinterpret_cast<float4*>(e.out_f32 + m * N + nb) = make_float4(v[0], v[1], v[2], v[3]);
     }
+}
+
+// SEPI_SWIGLU: gate tile `a` (packed features nb .. nb+3) and value tile `b` (packed features nb + 32 ..) of token m -> hi / lo planes
+// of out[m][swiglu_col(nb) ..], N = the PACKED width
+template <typename T>
+__device__ __forceinline__ void split_store_tile_swiglu(const f4& a, const f4& b, long long m, int nb, long long M, int N,
+                                                        const SplitEpi<T>& e, float& amax) {
+    typedef typename Vec<T>::t4 T4;
+    const float4 bg = e.bias ? *reinterpret_cast<const float4*>(e.bias + nb) : make_float4(0.f, 0.f, 0.f, 0.f);
+    const float4 bv = e.bias ? *reinterpret_cast<const float4*>(e.bias + nb + 32) : make_float4(0.f, 0.f, 0.f, 0.f);
+    const float g[4] = {a[0] * e.inv_wscale + bg.x, a[1] * e.inv_wscale + bg.y, a[2] * e.inv_wscale + bg.z, a[3] * e.inv_wscale + bg.w};
+    const float v[4] = {b[0] * e.inv_wscale + bv.x, b[1] * e.inv_wscale + bv.y, b[2] * e.inv_wscale + bv.z, b[3] * e.inv_wscale + bv.w};
+    T4 h, l;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        float am = 0.f;
+        const float p = swiglu_pair(g[r], v[r], am);
+        if (IsF16<T>::value) amax = fmaxf(amax, am);
+        T x0, x1;
+        split2<T>(p, x0, x1);
+        h[r] = x0; l[r] = x1;
+    }
+    if (m >= M) return;
+    const long long o = m * (N >> 1) + swiglu_col(nb);
+    *reinterpret_cast<T4*>(e.out_hi + o) = h;
+    *reinterpret_cast<T4*>(e.out_lo + o) = l;
 }
 
 // ---- C[M][N] = (A_hi + A_lo)[M][K] . (W_hi + W_lo)[N][K]^T on three MFMAs per product -----------------------------------------
@@ -261,6 +287,15 @@ __global__ __launch_bounds__(256, 2) void gemm_split_kernel(const T* __restrict_
     }
     // D tile (ni, mi) transposed: lane (fg, fj) holds features n0 + wc*64 + ni*16 + 4 fg + r of token m0 + wr*64 + mi*16 + fj
     float amax = 0.f;
+    if constexpr (EPI == SEPI_SWIGLU) {   // (N = 8192: whole tiles) gate fragments ni = 0, 1 with their value fragments ni + 2
+#pragma unroll
+        for (int ni = 0; ni < 2; ++ni) {
+            const int nb = n0 + wc * 64 + ni * 16 + fg * 4;
+#pragma unroll
+            for (int mi = 0; mi < 4; ++mi)
+                split_store_tile_swiglu<T>(acc[mi][ni], acc[mi][ni + 2], m0 + wr * 64 + mi * 16 + fj, nb, M, N, e, amax);
+        }
+    } else {
 #pragma unroll
     for (int ni = 0; ni < 4; ++ni) {
         const int nb = n0 + wc * 64 + ni * 16 + fg * 4;
@@ -269,7 +304,8 @@ __global__ __launch_bounds__(256, 2) void gemm_split_kernel(const T* __restrict_
         for (int mi = 0; mi < 4; ++mi)
             split_store_tile<T, EPI>(acc[mi][ni], m0 + wr * 64 + mi * 16 + fj, nb, M, N, e, amax);
     }
-    if (IsF16<T>::value && (EPI == SEPI_QKV || EPI == SEPI_GELU) && e.ovf) {
+    }
+    if (IsF16<T>::value && (EPI == SEPI_QKV || EPI == SEPI_GELU || EPI == SEPI_SWIGLU) && e.ovf) {
         if (__any(amax >= 65488.f) && lane == 0) atomicOr(e.ovf, EPI == SEPI_QKV ? 2 : 4);
     }
 #undef SP_FETCH
@@ -371,7 +407,49 @@ __global__ __launch_bounds__(512, 1) void gemm_split_dma_kernel(const T* __restr
     // Round 6: the epilogues leave through LDS as whole rows (vit_gemm_wide.h, gemm_wide_kernel: one workgroup per CU, nothing overlaps the
     // epilogue, and its 8-byte pieces -- 16 tokens x 32 B per store instruction -- ran at 1.5 TB/s).  The stages are dead here.
     static_assert(2 * SD_M * SD_OPITCH <= SD_STAGES * SD_STAGE_BYTES && SD_M * SD_FPITCH <= SD_STAGES * SD_STAGE_BYTES, "staged tile must fit");
-    if (STAGED && (EPI == SEPI_GELU || (EPI == SEPI_QKV && n0 < 2 * e.D))) {
+    if constexpr (EPI == SEPI_SWIGLU) {
+        // the w12 GEMM of ViT-g: a wave's 64 packed columns are 32 gate columns (ni = 0, 1) and their 32 value columns (ni + 2); the
+        // 256 x 64 hidden tile leaves as hi and lo planes, 128-byte rows of each plane: 8 lanes per row and plane
+        static_assert(STAGED, "SEPI_SWIGLU has no direct-store form");
+        constexpr int HP = SD_N + 8;   // staged hidden rows: 64 values x 2 B + 8
+        static_assert(2 * SD_M * HP <= SD_STAGES * SD_STAGE_BYTES, "staged hidden planes must fit");
+        __syncthreads();
+        unsigned char* const lo_plane = stages + SD_M * HP;
+#pragma unroll
+        for (int ni = 0; ni < 2; ++ni) {
+            const int cb = wc * 64 + ni * 16 + fg * 4, hb = wc * 32 + ni * 16 + fg * 4;
+            const float4 bg = e.bias ? *reinterpret_cast<const float4*>(e.bias + n0 + cb) : make_float4(0.f, 0.f, 0.f, 0.f);
+            const float4 bv = e.bias ? *reinterpret_cast<const float4*>(e.bias + n0 + cb + 32) : make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+            for (int mi = 0; mi < 4; ++mi) {
+                const f4 &a = acc[mi][ni], &b = acc[mi][ni + 2];
+                const float g[4] = {a[0] * e.inv_wscale + bg.x, a[1] * e.inv_wscale + bg.y, a[2] * e.inv_wscale + bg.z, a[3] * e.inv_wscale + bg.w};
+                const float v[4] = {b[0] * e.inv_wscale + bv.x, b[1] * e.inv_wscale + bv.y, b[2] * e.inv_wscale + bv.z, b[3] * e.inv_wscale + bv.w};
+                T4 h, l;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    float am = 0.f;
+                    const float p = swiglu_pair(g[r], v[r], am);
+                    if (IsF16<T>::value) amax = fmaxf(amax, am);
+                    T x0, x1;
+                    split2<T>(p, x0, x1);
+                    h[r] = x0; l[r] = x1;
+                }
+                const int off = (wr * 64 + mi * 16 + fj) * HP + hb * 2;
+                *reinterpret_cast<T4*>(stages + off) = h;
+                *reinterpret_cast<T4*>(lo_plane + off) = l;
+            }
+        }
+        __syncthreads();
+        const int plane = (tid >> 3) & 1, piece = tid & 7, NH = N >> 1;
+        T* const dst = (plane ? e.out_lo : e.out_hi) + (n0 >> 1) + piece * 8;
+#pragma unroll 4
+        for (int it = 0; it < SD_M / 32; ++it) {
+            const int row = it * 32 + (tid >> 4);
+            const uint4 v = staged16(stages + plane * (SD_M * HP) + row * HP + piece * 16);
+            if (m0 + row < M) *reinterpret_cast<uint4*>(dst + (m0 + row) * NH) = v;
+        }
+    } else if (STAGED && (EPI == SEPI_GELU || (EPI == SEPI_QKV && n0 < 2 * e.D))) {
         // hi and lo planes of the 256 x 128 tile, 16-bit, then 256-byte rows of each plane: 16 lanes per row and plane
         __syncthreads();
         const int which = EPI == SEPI_QKV ? n0 / e.D : 0;
@@ -511,7 +589,7 @@ __global__ __launch_bounds__(512, 1) void gemm_split_dma_kernel(const T* __restr
                 split_store_tile<T, EPI>(acc[mi][ni], m0 + wr * 64 + mi * 16 + fj, nb, M, N, e, amax);
         }
     }
-    if (IsF16<T>::value && (EPI == SEPI_QKV || EPI == SEPI_GELU) && e.ovf) {
+    if (IsF16<T>::value && (EPI == SEPI_QKV || EPI == SEPI_GELU || EPI == SEPI_SWIGLU) && e.ovf) {
         if (__any(amax >= 65488.f) && lane == 0) atomicOr(e.ovf, EPI == SEPI_QKV ? 2 : 4);
     }
 }

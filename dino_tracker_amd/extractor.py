@@ -47,7 +47,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
-from ._lib import VIT_ATTENTION_V4, VIT_GEMM_WIDE_V1, VIT_GEMM_WS_V1, VIT_NO_LN_FUSION, VIT_BF16, VIT_CHECK_RANGE, VIT_TILED_GEMMS, VitLayer, VitModel, check, lib
+from ._lib import VIT_FFN_SWIGLU, VIT_ATTENTION_V4, VIT_GEMM_WIDE_V1, VIT_GEMM_WS_V1, VIT_NO_LN_FUSION, VIT_BF16, VIT_CHECK_RANGE, VIT_TILED_GEMMS, VitLayer, VitModel, check, lib
 from .synth import VIT_CONFIGS, make_vit_weights
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)
@@ -87,7 +87,7 @@ class VitExtractor(nn.Module):
         self.gemm_wide_v1 = os.environ.get("DTK_VIT_GEMM_WIDE_V1", "0") == "1"   # the LDS-DMA GEMMs with round 5's direct-store epilogues (A / B; bit-identical)
         self.frame_batch = 0            # frames per pass of the encoder; 0 = the library's default
         if model_name not in VIT_CONFIGS:
-            raise NotImplementedError(f"{model_name}: the HIP encoder covers dinov2_vit{{s,b,l}}14 (d_head 64)")
+            raise NotImplementedError(f"{model_name}: the HIP encoder covers dinov2_vit{{s,b,l,g}}14 (d_head 64)")
         self.model_name, self.stride, self.device = model_name, stride, device
         self.cfg = VIT_CONFIGS[model_name]
         if state_dict is None and os.environ.get("DTK_DINOV2_WEIGHTS"):
@@ -98,6 +98,9 @@ class VitExtractor(nn.Module):
             raise RuntimeError("no DINOv2 weights: pass state_dict=, set $DTK_DINOV2_WEIGHTS to a checkpoint in "
                                "upstream naming, or ask for random_seed= explicitly (torch.hub needs the network)")
         self.n_layers = self.get_n_layers()
+        self.swiglu = self.cfg.get("ffn") == "swiglu"   # ViT-g: mlp.w12 / mlp.w3 (upstream SwiGLUFFNFused) instead of mlp.fc1 / mlp.fc2
+        # blocks present in the state dict (a truncated one serves the layers it has: tests need not build 40 blocks)
+        self.n_blocks = sum(1 for i in range(self.n_layers) if f"blocks.{i}.norm1.weight" in state_dict)
         self.tiled_gemms = False  # run every GEMM on the tiled kernel (dtk_vit_model.flags; cross-check in the tests)
         self._sd = {k: v.detach().to(device=device, dtype=torch.float32).contiguous() for k, v in state_dict.items()
                     if k.startswith(("cls_token", "pos_embed", "patch_embed.", "blocks."))}
@@ -185,16 +188,29 @@ class VitExtractor(nn.Module):
                 self._wcache[ck] = (scale, planes)
             return self._wcache[ck]
 
-        for i in range(depth):
+        def pack_w12(t):
+            """Rows of mlp.w12.weight [2 hid][D] / entries of mlp.w12.bias in the order the SwiGLU epilogue pairs them (include/dtk.h,
+            dtk_vit_model.ffn): groups of 32 gate rows, each followed by its 32 value rows."""
+            hid = self.cfg["hidden"]
+            gate, value = t[:hid].reshape(hid // 32, 32, *t.shape[1:]), t[hid:].reshape(hid // 32, 32, *t.shape[1:])
+            return torch.stack((gate, value), dim=1).reshape(t.shape).contiguous()
+
+        if self.swiglu:   # packed once per extractor (fp32): every operand type and the split planes are cut from this copy
+            for i in range(self.n_blocks):
+                for kind in ("weight", "bias"):
+                    if f"blocks.{i}.mlp.w12p.{kind}" not in sd:
+                        sd[f"blocks.{i}.mlp.w12p.{kind}"] = pack_w12(sd[f"blocks.{i}.mlp.w12.{kind}"])
+        fc1, fc2 = ("mlp.w12p", "mlp.w3") if self.swiglu else ("mlp.fc1", "mlp.fc2")
+        for i in range(self.n_blocks):
             p = f"blocks.{i}."
             L = arr[i]
             L.ln1_w, L.ln1_b = f32(p + "norm1.weight"), f32(p + "norm1.bias")
             L.qkv_b, L.proj_b = f32(p + "attn.qkv.bias"), f32(p + "attn.proj.bias")
             L.ls1 = f32(p + "ls1.gamma")
             L.ln2_w, L.ln2_b = f32(p + "norm2.weight"), f32(p + "norm2.bias")
-            L.fc1_b, L.fc2_b = f32(p + "mlp.fc1.bias"), f32(p + "mlp.fc2.bias")
+            L.fc1_b, L.fc2_b = f32(p + fc1 + ".bias"), f32(p + fc2 + ".bias")
             L.ls2 = f32(p + "ls2.gamma")
-            names = [p + "attn.qkv.weight", p + "attn.proj.weight", p + "mlp.fc1.weight", p + "mlp.fc2.weight"]
+            names = [p + "attn.qkv.weight", p + "attn.proj.weight", p + fc1 + ".weight", p + fc2 + ".weight"]
             if i in split_blocks:
                 scale, planes = split16(names)
                 (L.qkv_w, L.qkv_w_lo), (L.proj_w, L.proj_w_lo), (L.fc1_w, L.fc1_w_lo), (L.fc2_w, L.fc2_w_lo) = \
@@ -253,6 +269,8 @@ class VitExtractor(nn.Module):
         if want == "taps":   # the mean of the block outputs of `taps` in ONE pass (dtk_vit_model.tap_out); layer = the deepest of them
             taps = sorted({range(self.n_layers)[int(t)] for t in taps})
             layer = taps[-1]
+        if layer >= self.n_blocks:
+            raise ValueError(f"layer {layer}: the state dict holds blocks 0 .. {self.n_blocks - 1} only")
 
         def run(operand_dtype, split_blocks, frames=frames, n=n):
             if self.attention_v2:
@@ -266,7 +284,8 @@ class VitExtractor(nn.Module):
                          self._sd["patch_embed.proj.weight"].data_ptr(),
                          self._sd["patch_embed.proj.bias"].data_ptr(), cls_pos.data_ptr(), pos.data_ptr(), ms.data_ptr(),
                          ctypes.cast(self._build_layers(operand_dtype, split_blocks), ctypes.POINTER(VitLayer)),
-                         int(self.frame_batch), overflow.data_ptr(), None, 0, 0.0)
+                         int(self.frame_batch), overflow.data_ptr(), None, 0, 0.0,
+                         VIT_FFN_SWIGLU if self.swiglu else 0, self.cfg["hidden"] if self.swiglu else 0)
             tap_out = None
             if want == "taps":
                 tap_out = torch.zeros((n, S, D), dtype=torch.float32, device=self.device)

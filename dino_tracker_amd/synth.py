@@ -6,7 +6,7 @@ the golden-fixture script (tests/golden/make_golden.py) see bit-identical inputs
 """
 from __future__ import annotations
 
-from typing import Dict
+from typing import Dict, Optional
 
 import torch
 import torch.nn.functional as F
@@ -108,17 +108,20 @@ VIT_CONFIGS = {  # models/extractor.py:183-222
     "dinov2_vits14": dict(dim=384, depth=12, heads=6),
     "dinov2_vitb14": dict(dim=768, depth=12, heads=12),
     "dinov2_vitl14": dict(dim=1024, depth=24, heads=16),
+    # upstream vit_giant2: ffn_layer="swiglufused", hidden = (int(4 * 1536 * 2 / 3) + 7) // 8 * 8 (mlp.w12 / mlp.w3 instead of fc1 / fc2)
+    "dinov2_vitg14": dict(dim=1536, depth=40, heads=24, ffn="swiglu", hidden=4096),
 }
 
 
 def make_vit_weights(model_name: str, seed: int = 2, pos_grid: int = 37, patch: int = 14,
-                     layerscale: float = 1.0) -> Dict[str, torch.Tensor]:
+                     layerscale: float = 1.0, nblocks: Optional[int] = None) -> Dict[str, torch.Tensor]:
     """Seeded random weights with upstream's parameter names (no checkpoint exists in this environment).
     `layerscale` is the mean of the LayerScale gammas: 1.0 is the hub models' init_values; with untrained attention
     (near-uniform averaging) that makes every token collapse onto a common vector, unlike trained DINOv2 features,
-    so the benchmark uses a small value that keeps the residual stream dominated by the patch content."""
+    so the benchmark uses a small value that keeps the residual stream dominated by the patch content.
+    `nblocks`: only the first blocks (the draws run block by block, so they equal the full model's)."""
     cfg = VIT_CONFIGS[model_name]
-    d, depth = cfg["dim"], cfg["depth"]
+    d, depth = cfg["dim"], cfg["depth"] if nblocks is None else min(int(nblocks), cfg["depth"])
     g = torch.Generator().manual_seed(seed)
 
     def tn(*shape, std=0.02):
@@ -141,10 +144,17 @@ def make_vit_weights(model_name: str, seed: int = 2, pos_grid: int = 37, patch: 
         sd[p + "ls1.gamma"] = layerscale * (1.0 + tn(d, std=0.1))  # upstream hub models: init_values=1.0
         sd[p + "norm2.weight"] = 1.0 + tn(d, std=0.1)
         sd[p + "norm2.bias"] = tn(d, std=0.05)
-        sd[p + "mlp.fc1.weight"] = tn(4 * d, d, std=0.04)
-        sd[p + "mlp.fc1.bias"] = tn(4 * d)
-        sd[p + "mlp.fc2.weight"] = tn(d, 4 * d, std=0.03)
-        sd[p + "mlp.fc2.bias"] = tn(d)
+        if cfg.get("ffn") == "swiglu":
+            hid = cfg["hidden"]
+            sd[p + "mlp.w12.weight"] = tn(2 * hid, d, std=0.04)
+            sd[p + "mlp.w12.bias"] = tn(2 * hid)
+            sd[p + "mlp.w3.weight"] = tn(d, hid, std=0.03)
+            sd[p + "mlp.w3.bias"] = tn(d)
+        else:
+            sd[p + "mlp.fc1.weight"] = tn(4 * d, d, std=0.04)
+            sd[p + "mlp.fc1.bias"] = tn(4 * d)
+            sd[p + "mlp.fc2.weight"] = tn(d, 4 * d, std=0.03)
+            sd[p + "mlp.fc2.bias"] = tn(d)
         sd[p + "ls2.gamma"] = layerscale * (1.0 + tn(d, std=0.1))
     return sd
 

@@ -95,7 +95,7 @@ typedef struct dtk_vit_layer {
 } dtk_vit_layer;
 
 typedef struct dtk_vit_model {
-    int32_t D, heads;             /* d_head = D / heads must be 64 (ViT-S/B/L) */
+    int32_t D, heads;             /* d_head = D / heads must be 64 (ViT-S/B/L/g); D <= 1536 */
     int32_t depth;                /* number of blocks to run = hooked layer + 1 (models/extractor.py:137-150) */
     int32_t patch, stride;        /* 14, 7 (models/extractor.py:41-55) */
     float ln_eps;                 /* 1e-6 */
@@ -121,7 +121,21 @@ typedef struct dtk_vit_model {
     float* tap_out;
     uint64_t tap_mask;
     float tap_scale;
+    /* The feed-forward of the blocks.  DTK_VIT_FFN_GELU (0, what a zero-initialised caller gets): fc2(GELU(fc1 x)), hidden = 4 D.
+     * DTK_VIT_FFN_SWIGLU (ViT-g/14, upstream vit_giant2 with SwiGLUFFNFused: D = 1536, hidden = 4096):
+     *     x1, x2 = w12(x).chunk(2);  y = w3(silu(x1) * x2),   mlp.w12 [2 hidden][D] + bias, mlp.w3 [D][hidden] + bias.
+     * dtk_vit_layer.fc2_w / fc2_b are then w3, and fc1_w / fc1_b (and fc1_w_lo) the PACKED w12 / b12: row-interleaved in groups of
+     * 32 so that a gate row and its value row fall into the same lane of the GEMM's accumulators --
+     *     packed row 64 g + i      = w12 row 32 g + i            (gate,  i = 0 .. 31)
+     *     packed row 64 g + 32 + i = w12 row hidden + 32 g + i   (value),            g = 0 .. hidden / 32 - 1
+     * (every GEMM form gives a wave 64 consecutive columns as four 16-wide fragments: gate fragments 0, 1 meet value fragments 2, 3).
+     * One packed copy serves every kernel form; the epilogue writes hidden [rows][hidden], 128 columns per 256 packed ones, and
+     * tracks the fp16 range of what it stores as overflow bit 4.  DTK_VIT_GEMM_WS_V1 / GEMM_WIDE_V1 are refused for such a model. */
+    int32_t ffn;
+    int32_t hidden;               /* 0 = 4 D (GELU); 4096 for SwiGLU */
 } dtk_vit_model;
+#define DTK_VIT_FFN_GELU 0
+#define DTK_VIT_FFN_SWIGLU 1
 
 #define DTK_VIT_TILED_GEMMS 1   /* run the K = 384 GEMMs on the tiled kernel too (cross-check in the tests) */
 #define DTK_VIT_BF16 2          /* operand type bf16 instead of fp16 (weights must then be bf16) */
@@ -170,7 +184,7 @@ int dtk_vit_attention_split(const void* q_hi, const void* q_lo, const void* k_hi
                             void* stream);
 
 /* ONE GEMM of a block on its own: C = A W^T with the epilogue of its role, on exactly the kernel dtk_vit_forward runs for a model
- * of width D (384, 768 or 1024) with the DTK_VIT_* bits `flags` (the GEMM bits: TILED_GEMMS, GEMM_WS_V1, GEMM_WIDE_V1,
+ * of width D (384, 768, 1024 or 1536) with the DTK_VIT_* bits `flags` (the GEMM bits: TILED_GEMMS, GEMM_WS_V1, GEMM_WIDE_V1,
  * NO_LN_FUSION).  The role fixes N x K and what is written:
  *   DTK_VIT_GEMM_QKV        3D x D    q / k [rows / S][D / 64][Sp][64], vt [rows / S][D / 64][64][Sp]; q scaled by log2(e) / 8.  rows is a
  *                                     multiple of S; the caller zeroes the padding s >= S (dtk_vit_forward does), it is not written
@@ -182,6 +196,10 @@ int dtk_vit_attention_split(const void* q_hi, const void* q_lo, const void* k_hi
  *   DTK_VIT_GEMM_FC2        D x 4D    as PROJ.  With ln_out set (D = 384, none of TILED_GEMMS / GEMM_WIDE_V1 / NO_LN_FUSION: where
  *                                     dtk_vit_forward fuses it) the update is NOT stored: ln_x [rows][D] += it and ln_out [rows][D] =
  *                                     LayerNorm(ln_x; ln_w, ln_b, ln_eps), 16-bit
+ *   DTK_VIT_GEMM_FC1_SWIGLU 8192 x 1536  D = 1536 only: w = the PACKED w12 (dtk_vit_model.ffn), bias the packed b12;
+ *                                     out [rows][4096] = silu(gate) * value, 16-bit (split: out, out_lo); ovf bit 4.  Refused with
+ *                                     GEMM_WS_V1 / GEMM_WIDE_V1 in flags
+ *   DTK_VIT_GEMM_FC2_SWIGLU 1536 x 4096  D = 1536 only: w3, otherwise as FC2 (no fused LayerNorm at this width)
  * a [rows][K] and w [N][K] are 16-bit in `operand_type`, bias / gamma fp32 [N].  ovf: optional device word, OR-ed with 2 (QKV) / 4
  * (FC1) when a stored value reaches the fp16 limit and with 1 by the fused LayerNorm (fp16 operands only; the caller zeroes it).
  * dtk_vit_gemm_split: the same roles on hi / lo planes (a, a_lo; w, w_lo = planes of w_scale * W; q .. vt_lo; out, out_lo); PROJ and
@@ -191,6 +209,8 @@ int dtk_vit_attention_split(const void* q_hi, const void* q_lo, const void* k_hi
 #define DTK_VIT_GEMM_PROJ 2
 #define DTK_VIT_GEMM_FC1 3
 #define DTK_VIT_GEMM_FC2 4
+#define DTK_VIT_GEMM_FC1_SWIGLU 5
+#define DTK_VIT_GEMM_FC2_SWIGLU 6
 typedef struct dtk_vit_gemm_args {
     int32_t role, D, flags, operand_type;
     int64_t rows;
