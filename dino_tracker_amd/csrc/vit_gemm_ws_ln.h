@@ -199,7 +199,7 @@ __global__ __launch_bounds__(256) void gemm_ws_ln_kernel(const T* __restrict__ A
                 if (it == 0 || lane < 32) {
                     const T4 d = *reinterpret_cast<const T4*>(sp + it * 512);
                     const float d0 = (float)d[0], d1 = (float)d[1], d2 = (float)d[2], d3 = (float)d[3];
-                    if (IsF16<T>::value) sat |= !(fmaxf(fmaxf(fabsf(d0), fabsf(d1)), fmaxf(fabsf(d2), fabsf(d3))) < 65504.f);
+                    sat |= update_saturated<T>(d0, d1, d2, d3);
                     v[it].x += d0; v[it].y += d1; v[it].z += d2; v[it].w += d3;
                     *reinterpret_cast<f4*>(e.ln_x + row * WL_N + it * 256 + lane * 4) = v[it];
                     s += (v[it].x + v[it].y) + (v[it].z + v[it].w);

@@ -14,7 +14,7 @@
 // 16 significant bits there (plain bf16 operands: 8).
 //
 // Kernels (simple, LDS-tiled, ~3x the matrix work of the fast path by construction; this is the strict mode, not the headline):
-//   layernorm_split_kernel   LayerNorm (+ a pending 16-bit update of a preceding FAST block) -> hi / lo planes
+//   layernorm_split_kernel   (vit_rowwise.h) LayerNorm (+ a pending 16-bit update of a preceding FAST block) -> hi / lo planes
 //   gemm_split_dma_kernel    256 x 128 x 32 tiles by LDS-DMA (ring of three 48 KB stages), the production form;
 //   gemm_split_kernel        128 x 128 x 32 tiles, register-prefetched (cross-check, DTK_VIT_TILED_GEMMS): hi / lo planes of A and W in LDS, MFMA 16x16x32 as
 //                            (W tile) x (token tile)^T so that a lane owns 4 consecutive features of one token (8-byte / 16-byte
@@ -66,63 +66,6 @@ __device__ __forceinline__ float gelu_erfc(float x) {
     const float c = p * t * __builtin_amdgcn_exp2f(-(z * z) * 1.4426950408889634f);   // erfc(|z|)
     const float h = 0.5f * x * c;
     return x >= 0.f ? x - h : h;
-}
-
-// ---- LayerNorm -> hi / lo planes ------------------------------------------------------------------------------------------
-template <typename T, int NIT = 4>   // NIT float4 of the row per lane: vit.hip, launch_layernorm_split
-__global__ __launch_bounds__(256) void layernorm_split_kernel(float* __restrict__ x, const T* __restrict__ delta,
-                                                              const float* __restrict__ gam, const float* __restrict__ bet,
-                                                              T* __restrict__ y_hi, T* __restrict__ y_lo, long long rows, int D,
-                                                              float eps, int* __restrict__ overflow) {
-    typedef typename Vec<T>::t4 T4;
-    operand_mode<T>();
-    const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const int lane = threadIdx.x & 63;
-    float* p = x + row * D;
-    float4 v[NIT];
-    float s = 0.f;
-    bool sat = false;
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-        const int c = lane * 4 + it * 256;
-        if (c < D) {
-            v[it] = *reinterpret_cast<const float4*>(p + c);
-            if (delta) {   // the pending update of a preceding fast block (a split block adds its updates in its own epilogues)
-                const T4 d = *reinterpret_cast<const T4*>(delta + row * D + c);
-                const float d0 = (float)d[0], d1 = (float)d[1], d2 = (float)d[2], d3 = (float)d[3];
-                if (IsF16<T>::value) sat |= !(fmaxf(fmaxf(fabsf(d0), fabsf(d1)), fmaxf(fabsf(d2), fabsf(d3))) < 65504.f);
-                v[it].x += d0; v[it].y += d1; v[it].z += d2; v[it].w += d3;
-                *reinterpret_cast<float4*>(p + c) = v[it];
-            }
-            s += (v[it].x + v[it].y) + (v[it].z + v[it].w);
-        }
-    }
-    if (IsF16<T>::value && overflow && __any(sat) && lane == 0) atomicOr(overflow, 1);
-    const float mean = wave_sum(s) / (float)D;
-    float q = 0.f;
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-        if (lane * 4 + it * 256 < D) {
-            const float a = v[it].x - mean, b = v[it].y - mean, cc = v[it].z - mean, d = v[it].w - mean;
-            q += (a * a + b * b) + (cc * cc + d * d);
-        }
-    }
-    const float rstd = rsqrtf(wave_sum(q) / (float)D + eps);
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-        const int c = lane * 4 + it * 256;
-        if (c < D) {
-            const float4 g = *reinterpret_cast<const float4*>(gam + c), b = *reinterpret_cast<const float4*>(bet + c);
-            const float r[4] = {(v[it].x - mean) * rstd * g.x + b.x, (v[it].y - mean) * rstd * g.y + b.y,
-                                (v[it].z - mean) * rstd * g.z + b.z, (v[it].w - mean) * rstd * g.w + b.w};
-            T4 h, l;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { T a, b2; split2<T>(r[e], a, b2); h[e] = a; l[e] = b2; }
-            *reinterpret_cast<T4*>(y_hi + row * D + c) = h;
-            *reinterpret_cast<T4*>(y_lo + row * D + c) = l;
-        }
-    }
 }
 
 // ---- epilogue of one TRANSPOSED 16 x 16 D tile: the lane holds features nb .. nb+3 of token m -------------------------------

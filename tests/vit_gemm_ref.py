@@ -32,7 +32,7 @@ import torch
 
 QKV, QKV_FACET, PROJ, FC1, FC2 = 0, 1, 2, 3, 4   # dtk_vit_gemm_args.role (dino_tracker_amd._lib.VIT_GEMM_*)
 ROLE_NAMES = {QKV: "qkv", QKV_FACET: "qkv_facet", PROJ: "proj", FC1: "fc1", FC2: "fc2"}
-# 0.125f * 1.4426950408889634f as csrc/vit.hip evaluates it: the fp32 literal times an exact power of two
+# 0.125f * 1.4426950408889634f as csrc/vit.hip evaluates it (VIT_QSCALE): the fp32 literal times an exact power of two
 QSCALE = 0.125 * float(torch.tensor(1.4426950408889634, dtype=torch.float32))
 C_ACC = 2.0
 U32 = 2.0 ** -24
