@@ -267,6 +267,10 @@ SIGNATURES = {
     "dtk_raft_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "dtk_raft_forward": (c_int, [ctypes.POINTER(RaftModel), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                  c_size_t, c_void_p]),
+    "dtk_jpeg_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "dtk_jpeg_coefficients": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "dtk_jpeg_encode": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p,
+                                c_void_p, c_void_p]),
 }
 
 _LIB = None

@@ -812,3 +812,65 @@ def resize_u8(frames: torch.Tensor, h: int, w: int, kx: Optional[torch.Tensor], 
                               _p(ky, torch.int32), _p(by, torch.int32), ksy, _p(u8_to_f32, torch.float32), int(out_form),
                               int(options), _p(out), _p(ws), nbytes, _stream()))
     return out
+
+
+# ---- video output (csrc/jpeg.hip): baseline JPEG of rendered frames; tables and header are video_out's ------------------------------
+JPEG_RESTART = 16
+JPEG_MCU_WORST_BYTES = 2 * 1244   # 6 blocks of at most 20 + 63 * 26 bits, every byte stuffed (docs/JPEG.md section 6)
+
+
+def _jpeg_frames(frames: torch.Tensor) -> Tuple[int, int, int]:
+    if frames.dim() != 4 or frames.shape[3] != 3 or frames.numel() == 0:
+        raise RuntimeError(f"dino_tracker_amd: frames must be [F, H, W, 3] uint8 with F, H, W >= 1, got {tuple(frames.shape)}")
+    return int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
+
+
+def _jpeg_qtables(qtables: torch.Tensor):
+    if tuple(qtables.shape) != (2, 64):
+        raise RuntimeError(f"dino_tracker_amd: qtables must be uint8 [2, 64] (zigzag order), got {tuple(qtables.shape)}")
+    return _p(qtables, torch.uint8)
+
+
+def jpeg_workspace_bytes(F: int, H: int, W: int) -> int:
+    """dtk_jpeg_workspace_bytes: device bytes dtk_jpeg_encode needs for F frames of H x W (0 for sizes it refuses)."""
+    return int(lib().dtk_jpeg_workspace_bytes(int(F), int(H), int(W)))
+
+
+def jpeg_worst_case_bytes(F: int, H: int, W: int, header_bytes: int) -> int:
+    """No stream of F frames is longer: header, 2488 bytes per MCU, a marker per interval (the last one's is EOI)."""
+    mcus = ((H + 15) // 16) * ((W + 15) // 16)
+    return F * (header_bytes + JPEG_MCU_WORST_BYTES * mcus + 2 * ((mcus + JPEG_RESTART - 1) // JPEG_RESTART))
+
+
+def jpeg_coefficients(frames: torch.Tensor, qtables: torch.Tensor) -> torch.Tensor:
+    """dtk_jpeg_coefficients: frames [F, H, W, 3] uint8, qtables uint8 [2, 64] -> int16 [F, MCUs, 6, 64], zigzag order."""
+    F, H, W = _jpeg_frames(frames)
+    mcus = ((H + 15) // 16) * ((W + 15) // 16)
+    coef = torch.empty((F, mcus, 6, 64), dtype=torch.int16, device=frames.device)
+    check(lib().dtk_jpeg_coefficients(_p(frames, torch.uint8), F, H, W, _jpeg_qtables(qtables), _p(coef), _stream()))
+    return coef
+
+
+def jpeg_encode(frames: torch.Tensor, qtables: torch.Tensor, header: torch.Tensor,
+                capacity: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """dtk_jpeg_encode: (uint8 [bytes] -- the F files one after the other --, int64 [F + 1] offsets, both on the device).
+    `capacity` is the size of the first output buffer (default: the worst case); ONE host read-back, the stream's length.  When
+    the stream does not fit, the call has written nothing and is repeated once with a buffer of exactly that length."""
+    F, H, W = _jpeg_frames(frames)
+    if header.dim() != 1 or header.numel() == 0:
+        raise RuntimeError(f"dino_tracker_amd: header must be uint8 [bytes], got {tuple(header.shape)}")
+    hb = int(header.numel())
+    dev = frames.device
+    ws = torch.empty(jpeg_workspace_bytes(F, H, W), dtype=torch.uint8, device=dev)
+    offsets = torch.empty(F + 1, dtype=torch.int64, device=dev)
+    needed = torch.empty(1, dtype=torch.int64, device=dev)
+    cap = jpeg_worst_case_bytes(F, H, W, hb) if capacity is None else max(int(capacity), 1)
+    for attempt in range(2):
+        out = torch.empty(cap, dtype=torch.uint8, device=dev)
+        check(lib().dtk_jpeg_encode(_p(frames, torch.uint8), F, H, W, _jpeg_qtables(qtables), _p(header, torch.uint8), hb, _p(out), cap,
+                                    _p(offsets), _p(needed), _p(ws), _stream()))
+        n = int(needed.item())                        # the read-back
+        if n <= cap:
+            return out[:n], offsets
+        cap = n
+    raise RuntimeError(f"dino_tracker_amd: jpeg_encode needs {n} bytes after a retry with as many")

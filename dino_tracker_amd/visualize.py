@@ -444,9 +444,24 @@ def visualize_trajectories_with_gt(video, pred_trajectories, gt_trajectories, pr
     return res
 
 
-def save_video(video, path: str, fps: int = 10) -> str:
-    """Writes [T, H, W, 3] uint8 as an mp4 through imageio when that imports; otherwise as PNG frames 00000.png ... in a folder
-    named like the file without its extension.  Returns what it wrote and says so."""
+def save_video(video, path: str, fps: int = 10, container: Optional[str] = None, quality: int = 90) -> str:
+    """Writes [T, H, W, 3] uint8.  container None: an mp4 through imageio when that imports; otherwise PNG frames 00000.png ... in a
+    folder named like the file without its extension.  container "avi": <path without extension>.avi, a Motion-JPEG AVI, and "jpg":
+    a folder of 00000.jpg ... named like the file without its extension -- both through the device JPEG encoder (video_out.py) at
+    `quality`; a device tensor is encoded where it is, without a trip to the host.  Returns what it wrote and says so."""
+    if container is not None:
+        from . import video_out
+        if container not in ("avi", "jpg"):
+            raise ValueError(f"save_video: container must be None, 'avi' or 'jpg', got {container!r}")
+        stem, frames = os.path.splitext(path)[0], len(video)
+        if container == "avi":
+            written = video_out.write_mjpeg_avi(video, stem + ".avi", fps=fps, quality=quality)
+            print(f"save_video: wrote {written} (Motion-JPEG avi, {frames} frames, {fps} fps, quality {quality}, "
+                  f"{os.path.getsize(written)} bytes)")
+        else:
+            written = video_out.write_jpeg_frames(video, stem, quality=quality)
+            print(f"save_video: wrote {frames} JPEG frames (quality {quality}) to {written}/")
+        return written
     video = video.cpu().numpy() if isinstance(video, torch.Tensor) else np.asarray(video)
     try:
         import imageio
@@ -472,6 +487,19 @@ def _load_video_u8(video_folder: str, num_frames: Optional[int] = 300) -> np.nda
     from PIL import Image
     files = sorted(list(Path(video_folder).glob("*.jpg")) + list(Path(video_folder).glob("*.png")))[:num_frames]
     return np.stack([np.asarray(Image.open(str(f)).convert("RGB")) for f in files])
+
+
+def _container_args(args) -> dict:
+    """--container / --quality as save_video's keywords; `auto` (and an args object without the flags) is save_video's default"""
+    container = getattr(args, "container", "auto")
+    return {"container": None if container == "auto" else container, "quality": getattr(args, "quality", 90)}
+
+
+def _add_container_flags(p: argparse.ArgumentParser) -> None:
+    p.add_argument("--container", choices=("auto", "avi", "jpg"), default="auto",
+                   help="auto: mp4 through imageio, PNG frames without it; avi: Motion-JPEG AVI and jpg: a folder of JPEG frames, "
+                        "both encoded on the device")
+    p.add_argument("--quality", type=int, default=90, help="JPEG quality 1 .. 100 of --container avi / jpg")
 
 
 @torch.no_grad()
@@ -510,7 +538,8 @@ def run(args, device: str = "cuda:0"):
     name = f"dotted_tracks_fps_{args.fps}.mp4" if ero is None else f"dotted_tracks_erosion_kernel_{ero}_fps_{args.fps}.mp4"
     frames = torch.from_numpy(video).to(device)
     dotted = plot_tracks_v2(frames, tracks[is_fg], occluded[is_fg], rainbow_colors=True, point_size=args.point_size)
-    written = [save_video(dotted, os.path.join(out_dir, name), fps=args.fps)]
+    how = _container_args(args)
+    written = [save_video(dotted, os.path.join(out_dir, name), fps=args.fps, **how)]
     if args.plot_trails:
         bg = torch.load(paths["bg_trajectories_file"], map_location="cpu")[:, start:end]
         bg = filter_bg_trajectories_for_homographies(bg, canonical_frame=args.canonical_frame)
@@ -523,7 +552,7 @@ def run(args, device: str = "cuda:0"):
         rainbow = plot_tracks_tails(frames, tracks[is_fg], occluded[is_fg], homogs, point_size=args.point_size,
                                     linewidth=args.linewidth, marker="D")
         name = f"rainbow_fps_{args.fps}.mp4" if ero is None else f"rainbow_erosion_kernel_{ero}_fps_{args.fps}.mp4"
-        written.append(save_video(rainbow, os.path.join(out_dir, name), fps=args.fps))
+        written.append(save_video(rainbow, os.path.join(out_dir, name), fps=args.fps, **how))
     print("Saved to", out_dir)
     return written
 
@@ -531,7 +560,7 @@ def run(args, device: str = "cuda:0"):
 @torch.no_grad()
 def save_prediction_vs_gt(args, device: str = "cuda:0"):
     """visualize_pred_vs_gt.py:70-106 on the layout of utils.add_config_paths: per start frame of the benchmark video one
-    pred_vs_gt_frame_idx_<f>_fps_<fps>.mp4 (or PNG folder, see save_video) in <data-path>/visualizations."""
+    pred_vs_gt_frame_idx_<f>_fps_<fps>.mp4 (or PNG folder, .avi or JPEG folder, see save_video) in <data-path>/visualizations."""
     paths = add_config_paths(args.data_path, {})
     with open(args.benchmark_pickle_path, "rb") as fh:
         benchmark_data = pickle.load(fh)
@@ -556,7 +585,8 @@ def save_prediction_vs_gt(args, device: str = "cuda:0"):
             assert os.path.exists(occ_file), f"occlusion_preds_{frame_idx}.npy does not exist"
             pred_occ = np.load(occ_file)
         video = visualize_trajectories_with_gt(frames, pred, gt, pred_occ, gt_occ, badja_vis_type=args.badja_vis_type)
-        written.append(save_video(video, os.path.join(out_dir, f"pred_vs_gt_frame_idx_{frame_idx}_fps_{args.fps}.mp4"), fps=args.fps))
+        written.append(save_video(video, os.path.join(out_dir, f"pred_vs_gt_frame_idx_{frame_idx}_fps_{args.fps}.mp4"), fps=args.fps,
+                                  **_container_args(args)))
     print("Saved to", out_dir)
     return written
 
@@ -573,6 +603,7 @@ def make_pred_vs_gt_parser() -> argparse.ArgumentParser:
     p.add_argument("--only-first-frame", action="store_true", help="only the query points of the first start frame")
     p.add_argument("--use-gt-occ", action="store_true", help="use the ground-truth occlusion for the predictions too")
     p.add_argument("--fps", type=int, default=10, help="fps=10 for TAP-Vid, fps=2 for BADJA")
+    _add_container_flags(p)
     return p
 
 
@@ -590,6 +621,7 @@ def make_parser() -> argparse.ArgumentParser:
     p.add_argument("--point-size", type=int, default=40)
     p.add_argument("--linewidth", type=float, default=1.5)
     p.add_argument("--plot-trails", action="store_true", default=False, help="also render the rainbow trails (needs homographies)")
+    _add_container_flags(p)
     return p
 
 

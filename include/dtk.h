@@ -911,6 +911,46 @@ size_t dtk_raft_workspace_bytes(int32_t N, int32_t H, int32_t W);
 int dtk_raft_forward(const dtk_raft_model* model, const float* image1, const float* image2, int32_t N, int32_t H, int32_t W,
                      int32_t num_flow_updates, int32_t mode, float* flow_out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Video output: baseline JPEG (SOF0, 8 bit, Y 2 x 2 + Cb + Cr: 4:2:0, one interleaved scan, restart interval
+ * DTK_JPEG_RESTART MCUs, the typical Huffman tables of Annex K) of rendered frames, for Motion-JPEG AVIs and frame folders.  The
+ * arithmetic is DEFINED in docs/JPEG.md and is integer throughout; the kernels never evaluate a cosine or a quality setting. -----
+ * frames [F][H][W][3] uint8 (interleaved RGB).  An MCU is 16 x 16 pixels, mw = ceil(W / 16), mh = ceil(H / 16), MCUs in raster order,
+ * blocks of an MCU in the order Y00 Y01 Y10 Y11 Cb Cr.  qtables: uint8 [2][64], the luma and the chroma quantisation table in ZIGZAG
+ * order, values 1 .. 255 -- the 64 bytes a DQT segment stores; a zero entry is the caller's error (a division by zero on the device
+ * yields garbage coefficients, nothing else).
+ *
+ * dtk_jpeg_coefficients: the transform stage alone.  coef_out int16 [F][mh mw][6][64], zigzag order, operation by operation:
+ *   colour:   Y = (19595 R + 38470 G + 7471 B + 32768) >> 16,  Cb = (-11059 R - 21709 G + 32768 B + 8388608 + 32767) >> 16,
+ *             Cr = (32768 R - 27439 G - 5329 B + 8388608 + 32767) >> 16  (arithmetic shifts).
+ *   edges:    Y(y, x) = Y(min(y, H - 1), min(x, W - 1)).  Chroma row r, column c averages the colour planes at rows 2 r', 2 r' + 1
+ *             (clamped to H - 1) with r' = min(r, ceil(H / 2) - 1) and columns 2 c, 2 c + 1 (clamped to W - 1):
+ *             (a + b + c + d + bias) >> 2, bias = 1 for even c, 2 for odd c.  So the last DOWNSAMPLED row repeats downwards.
+ *   dummy:    a Y block whose block column is >= ceil(W / 8) or whose block row is >= ceil(H / 8) is not transformed: its AC
+ *             coefficients are 0 and its DC is the quantised DC of the previous block of its MCU.
+ *   DCT:      samples - 128, the separable 13-bit fixed-point transform of docs/JPEG.md section 3, rows first (8 x the DCT).
+ *   quantise: q8 = 8 Q[k];  c >= 0: (c + q8 / 2) / q8;  c < 0: -((-c + q8 / 2) / q8), truncating divisions.
+ * dtk_jpeg_encode: transform, entropy coding, assembly.  header [header_bytes] is the caller's file header SOI .. SOS (device
+ *   pointer; it must declare DRI = DTK_JPEG_RESTART and the Annex K tables, docs/JPEG.md section 5) and is copied in front of
+ *   every frame's scan.  out receives the F files one after the other:  header, the restart intervals with FF D0+n (n = the
+ *   interval's index - 1 modulo 8) in front of all but the first, FF D9.  Within an interval: DC differences against the previous
+ *   block of the component (0 at the interval's start), run/size symbols with ZRL and EOB, bits MSB first, the last byte completed
+ *   with 1-bits, a 0x00 after every 0xFF data byte.  offsets int64 [F + 1]: file f is out[offsets[f] .. offsets[f + 1]);
+ *   *needed (int64) = offsets[F].  offsets and *needed are always written.  If *needed > out_capacity NOTHING is written to out and
+ *   the call still returns 0: the caller reads *needed and calls again with a buffer of that size.
+ *   workspace: dtk_jpeg_workspace_bytes(F, H, W) bytes, 256-byte aligned: the coefficients (768 bytes per MCU), one slot of
+ *   DTK_JPEG_INTERVAL_BYTES per restart interval (an interval's worst case: 16 MCUs x 6 blocks x (20 + 63 x 26) bits, doubled by
+ *   stuffing) and the interval tables -- about 13 bytes per pixel, so the caller bounds F by it.  No host synchronisation inside.
+ * Refused with DTK_E_INVALID before anything is launched: F < 1, H or W < 1, H or W > 65535, null pointers, header_bytes < 1;
+ *   dtk_jpeg_workspace_bytes returns 0 for such sizes. */
+#define DTK_JPEG_RESTART 16
+#define DTK_JPEG_INTERVAL_BYTES 39808 /* >= 2 * 16 * 6 * 1658 / 8 = 39792, rounded to 64 */
+size_t dtk_jpeg_workspace_bytes(int32_t F, int32_t H, int32_t W);
+int dtk_jpeg_coefficients(const uint8_t* frames, int32_t F, int32_t H, int32_t W, const uint8_t* qtables, int16_t* coef_out,
+                          void* stream);
+int dtk_jpeg_encode(const uint8_t* frames, int32_t F, int32_t H, int32_t W, const uint8_t* qtables, const uint8_t* header,
+                    int32_t header_bytes, uint8_t* out, size_t out_capacity, int64_t* offsets, int64_t* needed, void* workspace,
+                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif
