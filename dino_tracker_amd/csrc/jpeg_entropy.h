@@ -1,0 +1,174 @@
+// jpeg_entropy.h -- the sequential part of baseline-JPEG decoding (docs/JPEG_DECODE.md section 1): Huffman look-ups built from a DHT's
+// raw counts and symbols, an MSB-first bit reader over UNSTUFFED bytes, and the decode loop of one 8 x 8 block.  Plain C++ that
+// compiles for the host and for the device: the kernel in jpeg_decode.hip and the stand-alone host program tests/host/
+// jpeg_entropy_host.cpp (built with the sanitisers) run the same lines.
+//
+// What holds whatever the bytes and the tables contain (the tables the library is handed are validated by the caller, but nothing
+// below relies on it):
+//   * every iteration of the block loop advances the coefficient index by at least one or ends the block: at most 64 iterations per
+//     block, so a segment of M MCUs takes at most 64 * 6 * M -- inside the documented bound 8 * bytes + 64 * 6 * M;
+//   * the reader never touches a word beyond the one that holds the last valid bit plus one (jpg_word checks the index): past
+//     the end the window is zero and JPG_S_OVERRUN is set;
+//   * a coefficient index beyond 63 ends the block with JPG_S_INDEX, a window no code matches ends it with JPG_S_CODE;
+//   * every table index is masked or range-checked.
+#pragma once
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#define JPG_HD __host__ __device__ __forceinline__
+#else
+#define JPG_HD inline
+#endif
+
+// status bits (DTK_JPEG_S_* in dtk.h)
+#define JPG_S_CODE 1      // no code matches the next bits (or a DC category above 11)
+#define JPG_S_INDEX 2     // a run carried the coefficient index beyond 63
+#define JPG_S_OVERRUN 4   // bits were read past the segment's end
+#define JPG_S_LEFTOVER 8  // more than 7 unread bits at the segment's end
+#define JPG_S_RANGE 16    // |coefficient * Q| > 2047 (set by the pixel stage)
+#define JPG_S_SEGMENT 32  // a segment-table entry outside the stream or the frame's MCUs: nothing decoded
+
+constexpr int JPG_LOOK_BITS = 9;
+constexpr int JPG_TABLE_BYTES = 272;   // a raw table: 16 counts, then up to 256 symbols in code order
+
+struct JpgHuff {
+    uint16_t look[1 << JPG_LOOK_BITS];   // by the next 9 bits: (length << 8) | symbol of a code of at most 9 bits, else 0
+    int32_t maxcode[17];                 // [l], l = 1 .. 16: the largest code of length l, -1 where there is none
+    int32_t valoff[17];                  // [l]: index of the first symbol of length l minus its code
+    uint8_t vals[256];
+};
+
+// Build in two steps with a barrier between them on the device: lanes `lane`, `lane + n`, ... of n.  A single host thread calls
+// both with (0, 1).
+JPG_HD void jpg_huff_clear(JpgHuff* t, int lane, int n) {
+    for (int i = lane; i < (1 << JPG_LOOK_BITS); i += n) t->look[i] = 0;
+}
+JPG_HD void jpg_huff_fill(const uint8_t* raw, JpgHuff* t, int lane, int n) {
+    // every lane walks the 16 counts (cheap); the symbols are shared out
+    int code = 0, k = 0;
+    for (int len = 1; len <= 16; ++len) {
+        const int cnt = raw[len - 1];
+        if (lane == 0) {
+            t->maxcode[len] = cnt ? code + cnt - 1 : -1;
+            t->valoff[len] = k - code;
+        }
+        for (int i = lane; i < cnt; i += n) {
+            const int sym_at = k + i, c = code + i;
+            if (sym_at > 255) break;
+            const uint8_t sym = raw[16 + sym_at];
+            t->vals[sym_at] = sym;
+            if (len <= JPG_LOOK_BITS && (c >> len) == 0) {   // an over-subscribed length writes nothing
+                const int first = c << (JPG_LOOK_BITS - len), count = 1 << (JPG_LOOK_BITS - len);
+                for (int e = 0; e < count; ++e) t->look[first + e] = (uint16_t)((len << 8) | sym);
+            }
+        }
+        k += cnt;
+        code = (code + cnt) << 1;
+    }
+    if (lane == 0) t->maxcode[0] = -1, t->valoff[0] = 0;
+}
+
+// the unstuffed bytes of a segment (or of the part of it that is staged) as big-endian-read 32-bit words.  `words` holds at least
+// (avail_bits + 31) / 32 + 1 readable words, zero beyond the data.  The reader keeps the next bits in a 64-bit register, at least
+// 32 of them at any time, and fetches the word after those ONE STEP EARLY (`ahead`): the memory read a symbol needs was issued while
+// the symbol before it was decoded, so the only dependent read per symbol is the table look-up.
+struct JpgBits {
+    const uint32_t* words;
+    uint32_t avail_bits;
+    uint32_t pos;     // bits consumed
+    uint32_t limit;   // readable words
+    uint32_t next;    // index of the word after `ahead`
+    uint32_t ahead;   // the word that follows the bits in `acc`
+    uint64_t acc;     // the bits from `pos` on, left-aligned
+    int cnt;          // how many of them are valid: 33 .. 64
+};
+
+JPG_HD uint32_t jpg_bswap(uint32_t v) { return (v >> 24) | ((v >> 8) & 0xff00u) | ((v << 8) & 0xff0000u) | (v << 24); }
+JPG_HD uint32_t jpg_word(const JpgBits& b, uint32_t i) { return i < b.limit ? jpg_bswap(b.words[i]) : 0u; }
+
+JPG_HD void jpg_bits_start(JpgBits& b, const uint32_t* words, uint32_t avail_bits, uint32_t pos) {
+    b.words = words, b.avail_bits = avail_bits, b.pos = pos, b.limit = (avail_bits + 31u) / 32u + 1u;
+    const uint32_t w = pos >> 5, s = pos & 31u;
+    b.acc = (((uint64_t)jpg_word(b, w) << 32) | jpg_word(b, w + 1)) << s;
+    b.cnt = 64 - (int)s;
+    b.ahead = jpg_word(b, w + 2);
+    b.next = w + 3;
+}
+
+// the next 32 bits, MSB first; zero (and JPG_S_OVERRUN) when the position is at or beyond the end.  Bits of the window that lie
+// beyond the end are whatever follows the data in `words` -- the callers keep zeros there.
+JPG_HD uint32_t jpg_window(const JpgBits& b, int& status) {
+    if (b.pos >= b.avail_bits) {
+        status |= JPG_S_OVERRUN;
+        return 0u;
+    }
+    return (uint32_t)(b.acc >> 32);
+}
+
+JPG_HD void jpg_consume(JpgBits& b, int n) {   // 0 <= n <= 31
+    b.acc <<= n;
+    b.cnt -= n;
+    b.pos += (uint32_t)n;
+    if (b.cnt <= 32) {
+        b.acc |= (uint64_t)b.ahead << (32 - b.cnt);
+        b.cnt += 32;
+        b.ahead = jpg_word(b, b.next++);
+    }
+}
+
+// one symbol: its length (0: none matches) and value
+JPG_HD int jpg_symbol(const JpgHuff& t, uint32_t window, int& sym) {
+    const unsigned e = t.look[window >> (32 - JPG_LOOK_BITS)];
+    if (e) {
+        sym = (int)(e & 0xffu);
+        return (int)(e >> 8);
+    }
+    for (int len = JPG_LOOK_BITS + 1; len <= 16; ++len) {
+        const int code = (int)(window >> (32 - len));
+        if (code <= t.maxcode[len]) {
+            sym = t.vals[(code + t.valoff[len]) & 255];
+            return len;
+        }
+    }
+    return 0;
+}
+
+// s bits after the `len`-bit code at the top of the window, sign-extended as T.81 F.2.2.1 (s <= 15)
+JPG_HD int jpg_extend(uint32_t window, int len, int s) {
+    if (s == 0) return 0;
+    const int v = (int)((window << len) >> (32 - s));
+    return (v >> (s - 1)) ? v : v - (1 << s) + 1;
+}
+
+// Decode one block into out[64] (zigzag order, ZEROED by the caller).  `pred` is the component's DC predictor.  Returns the status
+// bits it met; JPG_S_CODE, JPG_S_INDEX and JPG_S_OVERRUN end the block where they happen.  `iters` counts loop iterations.
+JPG_HD int jpg_decode_block(JpgBits& b, const JpgHuff& dc, const JpgHuff& ac, int& pred, int16_t* out, uint32_t& iters) {
+    int status = 0, sym = 0;
+    ++iters;
+    uint32_t w = jpg_window(b, status);
+    int len = jpg_symbol(dc, w, sym);
+    if (status) return status;
+    if (len == 0 || sym > 11) return JPG_S_CODE;
+    pred = (int16_t)(pred + jpg_extend(w, len, sym));   // wraps to 16 bits: defined for any stream
+    jpg_consume(b, len + sym);
+    out[0] = (int16_t)pred;
+    int k = 1;
+    while (k < 64) {
+        ++iters;
+        w = jpg_window(b, status);
+        if (status) return status;
+        len = jpg_symbol(ac, w, sym);
+        if (len == 0) return JPG_S_CODE;
+        const int r = sym >> 4, s = sym & 15;
+        jpg_consume(b, len + s);
+        if (s == 0) {
+            if (r != 15) break;   // EOB
+            k += 16;              // ZRL
+            continue;
+        }
+        k += r;
+        if (k > 63) return JPG_S_INDEX;
+        out[k++] = (int16_t)jpg_extend(w, len, s);
+    }
+    return 0;
+}

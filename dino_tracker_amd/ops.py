@@ -874,3 +874,58 @@ def jpeg_encode(frames: torch.Tensor, qtables: torch.Tensor, header: torch.Tenso
             return out[:n], offsets
         cap = n
     raise RuntimeError(f"dino_tracker_amd: jpeg_encode needs {n} bytes after a retry with as many")
+
+
+# ---- video ingest (csrc/jpeg_decode.hip): baseline JPEG decoding; the header parser and the tables are video_in's -----------------
+JPEG_SEGMENT_FIELDS = 5
+JPEG_HUFF_BYTES = 272
+JPEG_S_CODE, JPEG_S_INDEX, JPEG_S_OVERRUN, JPEG_S_LEFTOVER, JPEG_S_RANGE, JPEG_S_SEGMENT = 1, 2, 4, 8, 16, 32
+
+
+def jpeg_decode_workspace_bytes(F: int, H: int, W: int) -> int:
+    """dtk_jpeg_decode_workspace_bytes: device bytes dtk_jpeg_pixels needs for F frames of H x W (0 for sizes it refuses)."""
+    return int(lib().dtk_jpeg_decode_workspace_bytes(int(F), int(H), int(W)))
+
+
+def jpeg_decode_coefficients(stream: torch.Tensor, segments, huffman: torch.Tensor, H: int, W: int
+                             ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """dtk_jpeg_decode_coefficients: stream uint8 [bytes] (device), segments int64 [S, 5] (a HOST array: frame, byte offset, byte
+    length, first MCU, MCU count -- checked on the host, uploaded here), huffman uint8 [F, 3, 2, 272] (device) ->
+    (int16 [F, MCUs, 6, 64] zigzag, int32 status [F]).  Coefficients of MCUs that no segment covers are zero."""
+    import numpy as np
+    seg = np.ascontiguousarray(np.asarray(segments, dtype=np.int64))
+    if seg.ndim != 2 or seg.shape[1] != JPEG_SEGMENT_FIELDS or seg.shape[0] < 1:
+        raise RuntimeError(f"dino_tracker_amd: segments must be int64 [S, {JPEG_SEGMENT_FIELDS}] with S >= 1, got {seg.shape}")
+    if huffman.dim() != 4 or tuple(huffman.shape[1:]) != (3, 2, JPEG_HUFF_BYTES):
+        raise RuntimeError(f"dino_tracker_amd: huffman must be uint8 [F, 3, 2, {JPEG_HUFF_BYTES}], got {tuple(huffman.shape)}")
+    if stream.dim() != 1 or stream.numel() == 0:
+        raise RuntimeError(f"dino_tracker_amd: stream must be uint8 [bytes], got {tuple(stream.shape)}")
+    F, H, W = int(huffman.shape[0]), int(H), int(W)
+    mcus = ((H + 15) // 16) * ((W + 15) // 16)
+    dev = stream.device
+    coef = torch.zeros((F, mcus, 6, 64), dtype=torch.int16, device=dev)
+    status = torch.empty(F, dtype=torch.int32, device=dev)
+    seg_dev = torch.from_numpy(seg).to(dev)
+    check(lib().dtk_jpeg_decode_coefficients(_p(stream, torch.uint8), int(stream.numel()), _p(seg_dev), seg.ctypes.data,
+                                             int(seg.shape[0]), _p(huffman, torch.uint8), F, H, W, _p(coef), _p(status), _stream()))
+    return coef, status
+
+
+def jpeg_pixels(coef: torch.Tensor, qtables: torch.Tensor, H: int, W: int, status: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dtk_jpeg_pixels: coef int16 [F, MCUs, 6, 64], qtables uint8 [F, 3, 64] (zigzag) -> uint8 [F, H, W, 3].  `status` (int32
+    [F]) receives JPEG_S_RANGE for frames with |coef * Q| > 2047."""
+    H, W = int(H), int(W)
+    mcus = ((H + 15) // 16) * ((W + 15) // 16)
+    if coef.dim() != 4 or tuple(coef.shape[1:]) != (mcus, 6, 64) or coef.shape[0] < 1:
+        raise RuntimeError(f"dino_tracker_amd: coef must be int16 [F, {mcus}, 6, 64] for {H} x {W}, got {tuple(coef.shape)}")
+    F = int(coef.shape[0])
+    if tuple(qtables.shape) != (F, 3, 64):
+        raise RuntimeError(f"dino_tracker_amd: qtables must be uint8 [{F}, 3, 64] (zigzag order), got {tuple(qtables.shape)}")
+    if status is not None and tuple(status.shape) != (F,):
+        raise RuntimeError(f"dino_tracker_amd: status must be int32 [{F}], got {tuple(status.shape)}")
+    dev = coef.device
+    ws = torch.empty(jpeg_decode_workspace_bytes(F, H, W), dtype=torch.uint8, device=dev)
+    out = torch.empty((F, H, W, 3), dtype=torch.uint8, device=dev)
+    check(lib().dtk_jpeg_pixels(_p(coef, torch.int16), _p(qtables, torch.uint8), F, H, W, _p(out), _p(status, torch.int32), _p(ws),
+                                _stream()))
+    return out

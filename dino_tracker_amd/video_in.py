@@ -1,0 +1,294 @@
+"""JPEG ingest on the device: the files' bytes go up once, and entropy decoding, dequantisation, inverse DCT, chroma upsampling and
+colour conversion run in libdtk (csrc/jpeg_decode.hip; the arithmetic is defined in docs/JPEG_DECODE.md and is bit-equal to Pillow's
+decoder for the files an encoder makes).  The host only reads headers:
+
+    parse_jpeg(data)                          (JpegHeader, None) for a file the device decodes, else (None, the reason)
+    plan_jpeg(datas)                          the headers of several files of one size as the arrays the library takes
+    decode_jpeg(files_or_bytes, device)       uint8 [T, H, W, 3] on the device
+    decode_jpeg_coefficients(...)             the entropy stage alone: (int16 [T, MCUs, 6, 64] zigzag, int32 status [T], plan)
+
+Decoded on the device: baseline sequential (SOF0), 8 bit, components 1, 2, 3 sampled 2x2 / 1x1 / 1x1, ONE interleaved scan (Ss = 0,
+Se = 63, Ah = Al = 0), 8-bit quantisation tables, any Huffman tables, any restart interval, no Adobe APP14 segment.  Everything else
+-- and every file whose header this parser cannot follow -- is reported with its reason and stays with the caller's host path."""
+from __future__ import annotations
+
+import io
+import os
+from dataclasses import dataclass
+from typing import List, Optional, Sequence, Tuple, Union
+
+import numpy as np
+import torch
+
+HUFF_BYTES = 272          # DTK_JPEG_HUFF_BYTES: 16 counts + up to 256 symbols
+SEGMENT_MAX_BYTES = 1 << 28
+
+
+@dataclass
+class JpegHeader:
+    height: int
+    width: int
+    qtables: np.ndarray          # uint8 [3, 64]: per component, zigzag order (as DQT stores them)
+    huffman: np.ndarray          # uint8 [3, 2, 272]: per component the DC and the AC table, counts then symbols
+    restart: int                 # MCUs per restart interval, 0: none
+    scan: Tuple[int, int]        # byte range of the entropy-coded data (RSTn markers included, EOI excluded)
+    segments: np.ndarray         # int64 [S, 4]: byte offset in the file, byte length, first MCU, MCU count
+
+    @property
+    def mcus(self) -> int:
+        return ((self.height + 15) // 16) * ((self.width + 15) // 16)
+
+
+_SOF_OTHERS = {0xC1: "extended sequential (SOF1)", 0xC2: "progressive (SOF2)", 0xC3: "lossless (SOF3)", 0xC5: "differential (SOF5)",
+               0xC6: "differential progressive (SOF6)", 0xC7: "differential lossless (SOF7)", 0xC9: "arithmetic coding (SOF9)",
+               0xCA: "arithmetic coding (SOF10)", 0xCB: "arithmetic coding (SOF11)", 0xCD: "arithmetic coding (SOF13)",
+               0xCE: "arithmetic coding (SOF14)", 0xCF: "arithmetic coding (SOF15)"}
+
+
+def _check_huffman(cls: int, counts: Sequence[int], vals: bytes) -> Optional[str]:
+    if sum(counts) > 256 or len(vals) != sum(counts):
+        return "DHT: more than 256 symbols, or the segment is short"
+    code = 0
+    for length, n in enumerate(counts, 1):
+        code += n
+        if code > (1 << length):
+            return f"DHT: length {length} is over-subscribed"
+        code <<= 1
+    if cls == 0 and any(v > 11 for v in vals):
+        return "DHT: a DC category above 11"
+    if cls == 1 and any((v & 15) > 10 for v in vals):
+        return "DHT: an AC size above 10"
+    return None
+
+
+def parse_jpeg(data) -> Tuple[Optional[JpegHeader], Optional[str]]:
+    """Walk SOI .. SOS of one file (bytes, memoryview or uint8 array).  (header, None) when the device decodes it, else (None, why)."""
+    buf = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data
+    n = int(buf.shape[0])
+    if n < 4 or buf[0] != 0xFF or buf[1] != 0xD8:
+        return None, "no SOI marker"
+    dqt, dht, restart, sof, adobe = {}, {}, 0, None, False
+    i = 2
+    while True:
+        if i + 4 > n or buf[i] != 0xFF:
+            return None, f"no marker at byte {i}"
+        marker = int(buf[i + 1])
+        if marker == 0xFF:          # a fill byte
+            i += 1
+            continue
+        if marker in _SOF_OTHERS:
+            return None, _SOF_OTHERS[marker]
+        if marker == 0x01 or 0xD0 <= marker <= 0xD9 or marker == 0x00:
+            return None, f"marker FF{marker:02X} before the scan"
+        length = (int(buf[i + 2]) << 8) | int(buf[i + 3])
+        if length < 2 or i + 2 + length > n:
+            return None, f"segment FF{marker:02X} at byte {i} runs past the file"
+        seg = bytes(buf[i + 4:i + 2 + length])
+        i += 2 + length
+        if marker == 0xDB:
+            k = 0
+            while k < len(seg):
+                if seg[k] >> 4:
+                    return None, "16-bit quantisation table"
+                if (seg[k] & 15) > 3 or k + 65 > len(seg):
+                    return None, "DQT: table id above 3, or the segment is short"
+                dqt[seg[k] & 15] = np.frombuffer(seg[k + 1:k + 65], dtype=np.uint8)
+                k += 65
+        elif marker == 0xC4:
+            k = 0
+            while k < len(seg):
+                if k + 17 > len(seg) or (seg[k] >> 4) > 1 or (seg[k] & 15) > 3:
+                    return None, "DHT: table class above 1, id above 3, or the segment is short"
+                counts = list(seg[k + 1:k + 17])
+                vals = seg[k + 17:k + 17 + sum(counts)]
+                why = _check_huffman(seg[k] >> 4, counts, vals)
+                if why:
+                    return None, why
+                dht[seg[k]] = bytes(counts) + vals
+                k += 17 + sum(counts)
+        elif marker == 0xDD:
+            if len(seg) != 2:
+                return None, "DRI: wrong length"
+            restart = (seg[0] << 8) | seg[1]
+        elif marker == 0xEE:
+            if seg[:5] == b"Adobe":
+                adobe = True
+        elif marker == 0xC0:
+            if sof is not None:
+                return None, "two SOF0 segments"
+            sof = seg
+        elif marker == 0xDA:
+            break
+    if adobe:
+        return None, "Adobe APP14 segment"
+    if sof is None or len(sof) < 6:
+        return None, "no SOF0 segment before the scan"
+    if sof[0] != 8:
+        return None, f"{sof[0]}-bit samples"
+    height, width, ncomp = (sof[1] << 8) | sof[2], (sof[3] << 8) | sof[4], sof[5]
+    if ncomp != 3 or len(sof) != 6 + 3 * ncomp:
+        return None, "grayscale (1 component)" if ncomp == 1 else f"{ncomp} components"
+    if height < 1 or width < 1:
+        return None, "zero height or width (DNL)"
+    comps = [(sof[6 + 3 * c], sof[7 + 3 * c], sof[8 + 3 * c]) for c in range(3)]
+    if [c[0] for c in comps] != [1, 2, 3]:
+        return None, f"component ids {[c[0] for c in comps]}, not 1 2 3"
+    if [c[1] for c in comps] != [0x22, 0x11, 0x11]:
+        names = {(0x11, 0x11, 0x11): "4:4:4", (0x21, 0x11, 0x11): "4:2:2"}
+        return None, f"sampling {names.get(tuple(c[1] for c in comps), [hex(c[1]) for c in comps])}, not 4:2:0"
+    if any(c[2] not in dqt for c in comps):
+        return None, "a component's quantisation table is not defined"
+    if len(seg) != 10 or seg[0] != 3:
+        return None, "several scans (the first does not hold all three components)"
+    if [seg[1], seg[3], seg[5]] != [1, 2, 3]:
+        return None, "scan components out of order"
+    if (seg[7], seg[8], seg[9]) != (0, 63, 0):
+        return None, "the scan is not Ss = 0, Se = 63, Ah = Al = 0"
+    huff = np.zeros((3, 2, HUFF_BYTES), dtype=np.uint8)
+    for c in range(3):
+        for cls, ident in ((0, seg[2 + 2 * c] >> 4), (1, 0x10 | (seg[2 + 2 * c] & 15))):
+            if ident not in dht:
+                return None, "a component's Huffman table is not defined"
+            raw = dht[ident]
+            huff[c, cls, :len(raw)] = np.frombuffer(raw, dtype=np.uint8)
+    # the entropy-coded data: FF 00 is data; FF D0 .. D7 split it; FF D9 ends it; anything else is not ours
+    body = buf[i:]
+    at = np.flatnonzero((body[:-1] == 0xFF) & (body[1:] != 0)) if body.shape[0] > 1 else np.zeros(0, dtype=np.int64)
+    kinds = body[at + 1]
+    end = n
+    if at.size and kinds[-1] == 0xD9:
+        end, at, kinds = i + int(at[-1]), at[:-1], kinds[:-1]      # whatever follows EOI is ignored, as decoders do
+    elif at.size and (kinds == 0xD9).any():
+        first = int(np.flatnonzero(kinds == 0xD9)[0])
+        end, at, kinds = i + int(at[first]), at[:first], kinds[:first]
+    if ((kinds < 0xD0) | (kinds > 0xD7)).any():
+        return None, "a marker other than RSTn inside the scan (several scans, fill bytes or damage)"
+    mcus = ((height + 15) // 16) * ((width + 15) // 16)
+    expected = -(-mcus // restart) - 1 if restart else 0
+    if at.size != expected:
+        return None, f"{at.size} restart markers, {expected} expected"
+    if at.size and not np.array_equal(kinds & 7, np.arange(at.size) & 7):
+        return None, "restart markers out of order"
+    starts = np.concatenate(([i], i + at + 2)).astype(np.int64)
+    ends = np.concatenate((i + at, [end])).astype(np.int64)
+    per = restart if restart else mcus
+    first = np.arange(starts.size, dtype=np.int64) * per
+    segments = np.stack([starts, ends - starts, first, np.minimum(per, mcus - first)], axis=1)
+    if int((ends - starts).max()) > SEGMENT_MAX_BYTES:
+        return None, "a segment longer than 256 MiB"
+    return JpegHeader(height, width, np.stack([dqt[c[2]] for c in comps]), huff, restart, (i, end), segments), None
+
+
+@dataclass
+class JpegPlan:
+    """what dtk_jpeg_decode_coefficients / dtk_jpeg_pixels take for F files of one size whose bytes lie one after the other"""
+    frames: int
+    height: int
+    width: int
+    segments: np.ndarray   # int64 [S, 5]: frame, byte offset in the stream, byte length, first MCU, MCU count
+    huffman: np.ndarray    # uint8 [F, 3, 2, 272]
+    qtables: np.ndarray    # uint8 [F, 3, 64]
+
+
+def plan_jpeg(datas: Sequence, offsets: Optional[Sequence[int]] = None) -> Tuple[Optional[JpegPlan], Optional[str]]:
+    """Parse every file; (plan, None) when all are eligible and of one size, else (None, "<index>: <reason>").  offsets[f]: where
+    file f starts in the stream the caller uploads (default: the files one after the other)."""
+    if not len(datas):
+        return None, "no files"
+    headers: List[JpegHeader] = []
+    for f, data in enumerate(datas):
+        h, why = parse_jpeg(data)
+        if h is None:
+            return None, f"file {f}: {why}"
+        if headers and (h.height, h.width) != (headers[0].height, headers[0].width):
+            return None, f"file {f}: {h.height} x {h.width}, file 0 is {headers[0].height} x {headers[0].width}"
+        headers.append(h)
+    if offsets is None:
+        offsets = np.concatenate(([0], np.cumsum([len(d) for d in datas])))[:-1]
+    segs = []
+    for f, (h, off) in enumerate(zip(headers, offsets)):
+        s = np.empty((h.segments.shape[0], 5), dtype=np.int64)
+        s[:, 0], s[:, 1], s[:, 2:] = f, h.segments[:, 0] + int(off), h.segments[:, 1:]
+        segs.append(s)
+    return JpegPlan(len(headers), headers[0].height, headers[0].width, np.concatenate(segs),
+                    np.stack([h.huffman for h in headers]), np.stack([h.qtables for h in headers])), None
+
+
+# ---- bytes: one pinned buffer, one upload --------------------------------------------------------------------------------------
+Source = Union[str, os.PathLike, bytes, bytearray, memoryview]
+
+
+def read_pinned(sources: Sequence[Source]) -> Tuple[torch.Tensor, List[np.ndarray]]:
+    """All files' bytes in ONE pinned uint8 buffer, and a view of each file in it."""
+    sizes = [len(s) if isinstance(s, (bytes, bytearray, memoryview)) else os.path.getsize(s) for s in sources]
+    pinned = torch.empty(max(1, sum(sizes)), dtype=torch.uint8, pin_memory=True)
+    whole = pinned.numpy()
+    views, at = [], 0
+    for s, n in zip(sources, sizes):
+        view = whole[at:at + n]
+        if isinstance(s, (bytes, bytearray, memoryview)):
+            view[:] = np.frombuffer(s, dtype=np.uint8)
+        else:
+            with open(s, "rb") as fh:
+                got = fh.readinto(memoryview(view))
+            if got != n:
+                raise OSError(f"{s}: read {got} of {n} bytes")
+        views.append(view)
+        at += n
+    return pinned, views
+
+
+def _device(device) -> torch.device:
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("dino_tracker_amd: the JPEG decoder needs a GPU device -- the hot path has no CPU fallback")
+    return device
+
+
+def _entropy(pinned: torch.Tensor, plan: JpegPlan, device: torch.device):
+    from . import ops
+    stream = pinned.to(device, non_blocking=True)
+    huff = torch.from_numpy(plan.huffman).to(device)
+    return ops.jpeg_decode_coefficients(stream, plan.segments, huff, plan.height, plan.width)
+
+
+def _planned(sources: Sequence[Source]) -> Tuple[torch.Tensor, List[np.ndarray], JpegPlan]:
+    pinned, views = read_pinned(sources)
+    plan, why = plan_jpeg(views)
+    if plan is None:
+        raise ValueError(f"decode_jpeg: not decodable on the device -- {why}")
+    return pinned, views, plan
+
+
+def decode_jpeg_coefficients(sources: Sequence[Source], device="cuda:0") -> Tuple[torch.Tensor, torch.Tensor, JpegPlan]:
+    """The entropy stage alone: (int16 [T, MCUs, 6, 64] in zigzag order, int32 status [T] -- ops.JPEG_S_* bits --, the plan)."""
+    device = _device(device)
+    pinned, _, plan = _planned(sources)
+    coef, status = _entropy(pinned, plan, device)
+    return coef, status, plan
+
+
+def decode_planned(pinned: torch.Tensor, views: List[np.ndarray], plan: JpegPlan, device, fallback: bool = True,
+                   with_status: bool = False):
+    from . import ops
+    device = _device(device)
+    coef, status = _entropy(pinned, plan, device)
+    qt = torch.from_numpy(plan.qtables).to(device)
+    out = ops.jpeg_pixels(coef, qt, plan.height, plan.width, status)
+    host_status = status.cpu()                       # the one host read
+    if fallback and bool(host_status.any()):
+        from PIL import Image
+        for f in torch.nonzero(host_status).flatten().tolist():
+            with Image.open(io.BytesIO(views[f].tobytes())) as img:
+                frame = np.asarray(img.convert("RGB") if img.mode != "RGB" else img)
+            out[f] = torch.from_numpy(np.ascontiguousarray(frame)).to(device)
+    return (out, host_status) if with_status else out
+
+
+def decode_jpeg(sources: Sequence[Source], device="cuda:0", fallback: bool = True, with_status: bool = False):
+    """uint8 [T, H, W, 3] on `device` from JPEG files (paths) or byte strings of one size.  ValueError with the reason when a file
+    is not of the kind the device decodes (module docstring).  After the launches ONE host read, the frames' status; a frame
+    whose status is not zero -- a damaged stream -- is decoded by Pillow instead and uploaded into its slot (`fallback`), which
+    raises what Pillow raises.  with_status: also the int32 [T] status as the device reported it (host tensor)."""
+    pinned, views, plan = _planned(sources)
+    return decode_planned(pinned, views, plan, device, fallback, with_status)

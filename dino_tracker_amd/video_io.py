@@ -1,4 +1,5 @@
-"""Video ingest on the device: frames are decoded by Pillow on the host, uploaded once as uint8, and LANCZOS-resized by libdtk
+"""Video ingest on the device: frames are decoded -- baseline 4:2:0 JPEG folders by libdtk (video_in.py, csrc/jpeg_decode.hip:
+the compressed bytes go up), everything else by Pillow on the host and uploaded once as uint8 -- and LANCZOS-resized by libdtk
 (csrc/resize.hip) with Pillow's own 8-bit arithmetic, so the result is bit-equal to `Image.resize(..., Image.LANCZOS)` followed by
 `ToTensor` -- what data/data_utils.py:79-104 (`load_video`) and :47-52 (`resize_tensor_frames_lanczos`) compute on the CPU.
 
@@ -9,6 +10,7 @@ from __future__ import annotations
 
 import functools
 import math
+import os
 from pathlib import Path
 from typing import Dict, Optional, Tuple
 
@@ -151,11 +153,31 @@ def _decode_pinned(files) -> Optional[torch.Tensor]:
     return buf
 
 
+def _decode_jpeg_device(files, device: torch.device) -> Optional[torch.Tensor]:
+    """uint8 [T, H, W, 3] on the device when every file is a JPEG the device decodes (video_in.parse_jpeg) and all are of one
+    size, else None: the routing is decided from the headers, before anything is uploaded.  DTK_JPEG_DECODE = host | device | auto
+    (the default, docs/MEASUREMENTS.md "JPEG decode"): `host` keeps Pillow for everything; `auto` and `device` both take the device
+    decoder for every eligible folder."""
+    mode = os.environ.get("DTK_JPEG_DECODE", "auto")
+    if mode not in ("auto", "device", "host"):
+        raise ValueError(f"DTK_JPEG_DECODE must be auto, device or host, got {mode!r}")
+    if mode == "host" or any(Path(f).suffix != ".jpg" for f in files):
+        return None
+    from . import video_in
+    pinned, views = video_in.read_pinned(files)
+    plan, _ = video_in.plan_jpeg(views)
+    if plan is None:
+        return None
+    return video_in.decode_planned(pinned, views, plan, device)
+
+
 def load_video(video_folder, resize=None, num_frames: Optional[int] = None, device="cuda:0") -> torch.Tensor:
     """data/data_utils.py:79-104 with the resize on the device: the frames of `video_folder` in file order (the first
-    `num_frames`), decoded on the host, uploaded once as uint8, LANCZOS-resized to `resize` = (h, w) and converted as ToTensor
-    does -> float32 [T, C, h, w] on `device`, bit-equal to the host path.  Frames that are not all RGB or all L of one size take
-    the host path (train.load_video) and are uploaded afterwards."""
+    `num_frames`) as uint8 on the device, LANCZOS-resized to `resize` = (h, w) and converted as ToTensor does -> float32
+    [T, C, h, w] on `device`, bit-equal to the host path.  A folder of baseline 4:2:0 JPEG files of one size is decoded on the device
+    from its compressed bytes (a frame whose stream is damaged is decoded by Pillow instead); other frames are decoded by Pillow on
+    the host and uploaded once.  Frames that are not all RGB or all L of one size take the host path (train.load_video) and are
+    uploaded afterwards."""
     device = torch.device(device)
     if device.type != "cuda":
         raise RuntimeError("dino_tracker_amd: video_io.load_video needs a GPU device -- the hot path has no CPU fallback")
@@ -163,6 +185,10 @@ def load_video(video_folder, resize=None, num_frames: Optional[int] = None, devi
     files = files[:num_frames] if num_frames is not None else files
     if not files:
         raise RuntimeError(f"dino_tracker_amd: no *.jpg / *.png frames in {video_folder}")
+    frames = _decode_jpeg_device(files, device)
+    if frames is not None:
+        h, w = (int(resize[0]), int(resize[1])) if resize is not None else (int(frames.shape[1]), int(frames.shape[2]))
+        return resize_lanczos(frames, h, w, out="f32")
     frames = _decode_pinned(files)
     if frames is None:
         from .train import load_video as host_load_video

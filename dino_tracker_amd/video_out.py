@@ -5,7 +5,8 @@ in docs/JPEG.md) and are written as a Motion-JPEG AVI or as a folder of 00000.jp
     write_mjpeg_avi(frames, path, fps)        RIFF AVI: hdrl (avih, strl: strh vids / MJPG, strf BITMAPINFOHEADER), movi of 00dc
                                               chunks -- one whole JPEG file each --, idx1
     write_jpeg_frames(frames, folder)         00000.jpg ..., the names load_video and the reference's loaders glob
-    read_mjpeg_avi(path)                      the strict inverse of write_mjpeg_avi: the JPEG byte strings
+    read_mjpeg_avi(path)                      the strict inverse of write_mjpeg_avi: the JPEG byte strings, or with device=...
+                                              the frames decoded on the device (video_in.py)
 
 The host builds what does not depend on the pixels: the quantisation tables of a quality (quant_tables) and the file header SOI ..
 SOS (jpeg_header).  Everything per pixel runs on the device; there is no CPU encoder here -- CPU tensors are refused, numpy
@@ -231,10 +232,12 @@ class AviError(ValueError):
     """read_mjpeg_avi: the file is not what write_mjpeg_avi writes; the message names the field"""
 
 
-def read_mjpeg_avi(path: str, with_info: bool = False):
+def read_mjpeg_avi(path: str, with_info: bool = False, device=None):
     """The JPEG byte strings of a Motion-JPEG AVI as write_mjpeg_avi lays it out (with_info: and a dict of frames, fps, width,
-    height).  Strict: every size and offset has to add up -- RIFF and LIST sizes against the file, chunk sizes against their
-    lists, the frame counts of avih and strh against the chunks, idx1 against the chunks' positions -- or AviError names it."""
+    height).  device: instead of the byte strings, the frames decoded on that device, uint8 [F, H, W, 3] (video_in.decode_jpeg:
+    no Pillow unless a frame's stream is damaged).  Strict: every size and offset has to add up -- RIFF and LIST sizes against the
+    file, chunk sizes against their lists, the frame counts of avih and strh against the chunks, idx1 against the chunks' positions
+    -- or AviError names it."""
     with open(path, "rb") as fh:
         data = fh.read()
 
@@ -290,6 +293,9 @@ def read_mjpeg_avi(path: str, with_info: bool = False):
     for i, (off, size_) in enumerate(where):
         entry = struct.unpack("<4sIII", data[x + 16 * i:x + 16 * i + 16])
         need(entry == (b"00dc", AVIIF_KEYFRAME, off, size_), f"idx1[{i}] = {entry}, the chunk is at {off} with {size_} bytes")
+    if device is not None:
+        from . import video_in
+        frames = video_in.decode_jpeg(frames, device)
     if with_info:
         return frames, {"frames": len(frames), "fps": strh[7], "width": strf[1], "height": strf[2]}
     return frames

@@ -951,6 +951,45 @@ int dtk_jpeg_encode(const uint8_t* frames, int32_t F, int32_t H, int32_t W, cons
                     int32_t header_bytes, uint8_t* out, size_t out_capacity, int64_t* offsets, int64_t* needed, void* workspace,
                     void* stream);
 
+/* ---- Video ingest: baseline JPEG DECODING (SOF0, 8 bit, components 1 2 3 sampled 2 x 2, 1 x 1, 1 x 1, one interleaved scan, 8-bit
+ * quantisation tables, the file's own Huffman tables, any restart interval).  The arithmetic is DEFINED in docs/JPEG_DECODE.md --
+ * libjpeg-turbo's default path: slow-integer IDCT, h2v2 "fancy" upsampling -- and is integer throughout.  The header is the CALLER's
+ * to parse and validate (dino_tracker_amd/video_in.py); the library sees tables and a table of segments. --------------------------
+ * dtk_jpeg_decode_coefficients: the entropy stage.  stream [stream_bytes]: the files' bytes (device).  A SEGMENT is a run of
+ *   entropy-coded bytes that starts byte-aligned with the DC predictors at 0 -- a restart interval without its RSTn marker, or a
+ *   whole scan -- and holds whole MCUs: int64 [n_segments][DTK_JPEG_SEGMENT_FIELDS] = frame, byte offset in stream, byte length,
+ *   first MCU, MCU count.  The table is passed twice: `segments` on the device (read by the kernel) and `segments_host`, the same
+ *   values in host memory, which are checked BEFORE anything is launched (the call never waits for the device).  The kernel repeats
+ *   the check on its own copy: an entry that does not fit sets DTK_JPEG_S_SEGMENT and decodes nothing.  Segments of one frame
+ *   must not overlap in MCUs (the caller's business: overlapping ones race on coef_out, nothing else).
+ *   huffman: uint8 [F][3][2][DTK_JPEG_HUFF_BYTES]: per frame and component the DC and the AC table as a DHT stores them, 16 counts
+ *   and the symbols in code order, zero-filled to 272 bytes.  The caller validates them (counts sum <= 256, no over-subscribed
+ *   length, DC symbols <= 11, AC sizes <= 10); the kernel is memory-safe for any content.
+ *   coef_out int16 [F][mh mw][6][64]: zigzag order, blocks Y00 Y01 Y10 Y11 Cb Cr, the encoder's layout.  Only the blocks of MCUs
+ *   that some segment covers are written.  status int32 [F]: zeroed, then the OR of DTK_JPEG_S_* over the frame's segments.  A
+ *   segment stops decoding at its first CODE / INDEX / OVERRUN fault; its remaining blocks are written as zeros.
+ * dtk_jpeg_pixels: dequantisation, inverse DCT, upsampling, colour.  qtables uint8 [F][3][64]: per frame and component, zigzag
+ *   order.  out uint8 [F][H][W][3] interleaved RGB.  status (may be null): DTK_JPEG_S_RANGE is ORed in where |coef * Q| > 2047;
+ *   the arithmetic is 32-bit wrap-around, so the output is defined for any coefficients.  workspace:
+ *   dtk_jpeg_decode_workspace_bytes(F, H, W) bytes, 256-byte aligned: the Y, Cb, Cr planes padded to whole MCUs (384 bytes per MCU).
+ * No host synchronisation inside.  Refused with DTK_E_INVALID before anything is launched: F < 1, H or W < 1 or > 65535, null
+ *   pointers, stream_bytes < 1, n_segments < 1, a segments_host entry outside the frames, the stream or the MCUs;
+ *   dtk_jpeg_decode_workspace_bytes returns 0 for such sizes. */
+#define DTK_JPEG_SEGMENT_FIELDS 5
+#define DTK_JPEG_HUFF_BYTES 272
+#define DTK_JPEG_S_CODE 1     /* no Huffman code matches the next bits */
+#define DTK_JPEG_S_INDEX 2    /* a run carried the coefficient index beyond 63 */
+#define DTK_JPEG_S_OVERRUN 4  /* bits were read past the segment's end */
+#define DTK_JPEG_S_LEFTOVER 8 /* more than 7 unread bits at the segment's end */
+#define DTK_JPEG_S_RANGE 16   /* |coefficient * Q| > 2047 */
+#define DTK_JPEG_S_SEGMENT 32 /* a segment entry outside the stream or the frame */
+size_t dtk_jpeg_decode_workspace_bytes(int32_t F, int32_t H, int32_t W);
+int dtk_jpeg_decode_coefficients(const uint8_t* stream, int64_t stream_bytes, const int64_t* segments, const int64_t* segments_host,
+                                 int32_t n_segments, const uint8_t* huffman, int32_t F, int32_t H, int32_t W, int16_t* coef_out,
+                                 int32_t* status, void* stream_handle);
+int dtk_jpeg_pixels(const int16_t* coef, const uint8_t* qtables, int32_t F, int32_t H, int32_t W, uint8_t* out, int32_t* status,
+                    void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
