@@ -9,7 +9,7 @@
 //                              anchor frame has med <= tau (occ = low) and a low frame is occluded whatever its median: only
 //                              the UNDECIDED frames (neither anchor nor low) need a median, and they need tau, i.e. the
 //                              anchor frames.  A query with no undecided frame (or no anchor) needs no anchor map at all.
-#include "common.h"
+#include "block_scan.h"
 
 namespace {
 
@@ -42,14 +42,11 @@ __global__ __launch_bounds__(256) void query_need_kernel(const float* __restrict
 // frame_cnt[a] = sources of anchor frame a = sum of need_w[n] over the queries with anchor (n, a)
 __global__ __launch_bounds__(256) void frame_weight_kernel(const float* __restrict__ cs, float th, int N, int T,
                                                            const int32_t* __restrict__ need_w, int32_t* __restrict__ frame_cnt) {
-    __shared__ int red[4];
     const int a = blockIdx.x;
     int c = 0;
     for (int n = threadIdx.x; n < N; n += 256) c += is_anchor(cs, th, n, T, a) ? need_w[n] : 0;
-    c = wave_sum_i(c);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) frame_cnt[a] = red[0] + red[1] + red[2] + red[3];
+    c = block_sum_i<4>(c);
+    if (threadIdx.x == 0) frame_cnt[a] = c;
 }
 
 // one block: counts[0] = pairs, counts[1] = emitted sources, counts[3] = open queries
@@ -57,16 +54,13 @@ __global__ __launch_bounds__(256) void finalize_needed_counts_kernel(const int32
                                                                      const int32_t* __restrict__ frame_off,
                                                                      const int32_t* __restrict__ need_w, int N, int T,
                                                                      int32_t* __restrict__ counts) {
-    __shared__ int red[4];
     int open = 0;
     for (int n = threadIdx.x; n < N; n += 256) open += need_w[n] > 0 ? 1 : 0;
-    open = wave_sum_i(open);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = open;
-    __syncthreads();
+    open = block_sum_i<4>(open);
     if (threadIdx.x == 0) {
         counts[0] = pair_off[N];
         counts[1] = frame_off[T];
-        counts[3] = red[0] + red[1] + red[2] + red[3];
+        counts[3] = open;
     }
 }
 
@@ -81,55 +75,30 @@ __global__ __launch_bounds__(256) void anchor_count_kernel(const float* __restri
 
 __global__ __launch_bounds__(256) void frame_count_kernel(const float* __restrict__ cs, float th, int N, int T,
                                                           int32_t* __restrict__ frame_cnt) {
-    __shared__ int red[4];
     const int a = blockIdx.x;
     int c = 0;
     for (int n = threadIdx.x; n < N; n += 256) c += is_anchor(cs, th, n, T, a) ? 1 : 0;
-    c = wave_sum_i(c);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) frame_cnt[a] = red[0] + red[1] + red[2] + red[3];
-}
-
-// block-wide inclusive scan of one int per thread (256 threads); returns inclusive prefix, *total = block sum
-__device__ __forceinline__ int block_scan_incl(int v, int* lds4, int* total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int y = __shfl_up(x, o, WAVE);
-        if (lane >= o) x += y;
-    }
-    __syncthreads();
-    if (lane == 63) lds4[w] = x;
-    __syncthreads();
-    int base = 0;
-    for (int i = 0; i < w; ++i) base += lds4[i];
-    *total = lds4[0] + lds4[1] + lds4[2] + lds4[3];
-    return x + base;
+    c = block_sum_i<4>(c);
+    if (threadIdx.x == 0) frame_cnt[a] = c;
 }
 
 // single block: out[0..n] = exclusive scan of in[0..n-1]; optionally count zeros
 __global__ __launch_bounds__(256) void exclusive_scan_kernel(const int32_t* __restrict__ in, int32_t* __restrict__ out,
                                                              int n, int32_t* __restrict__ zero_count) {
-    __shared__ int lds4[4];
     int carry = 0, zeros = 0;
     for (int i0 = 0; i0 < n; i0 += 256) {
         const int i = i0 + threadIdx.x;
         const int v = i < n ? in[i] : 0;
         if (i < n && v == 0) ++zeros;
         int total;
-        const int incl = block_scan_incl(v, lds4, &total);
-        if (i < n) out[i] = carry + incl - v;
+        const int excl = block_scan_excl<4>(v, total);
+        if (i < n) out[i] = carry + excl;
         carry += total;
     }
     if (threadIdx.x == 0) out[n] = carry;
     if (zero_count) {
-        zeros = wave_sum_i(zeros);
-        __syncthreads();
-        if ((threadIdx.x & 63) == 0) lds4[threadIdx.x >> 6] = zeros;
-        __syncthreads();
-        if (threadIdx.x == 0) *zero_count = lds4[0] + lds4[1] + lds4[2] + lds4[3];
+        zeros = block_sum_i<4>(zeros);
+        if (threadIdx.x == 0) *zero_count = zeros;
     }
 }
 
@@ -147,16 +116,15 @@ __global__ __launch_bounds__(256) void emit_sources_kernel(const float* __restri
                                                            int32_t* __restrict__ pair_frame,
                                                            int32_t* __restrict__ src_row, int32_t* __restrict__ tgt,
                                                            int32_t* __restrict__ out_idx) {
-    __shared__ int lds4[4];
     const int a = blockIdx.x;
     int carry = frame_off[a];
     for (int n0 = 0; n0 < N; n0 += 256) {
         const int n = n0 + threadIdx.x;
         const int flag = (n < N && is_anchor(cs, th, n, T, a)) ? 1 : 0;
         int total;
-        const int incl = block_scan_incl(flag, lds4, &total);
+        const int excl = block_scan_excl<4>(flag, total);
         if (flag) {
-            const int j = carry + incl - 1;  // position among the pairs sorted by anchor frame
+            const int j = carry + excl;  // position among the pairs sorted by anchor frame
             int rank = 0;
             for (int t = 0; t < a; ++t) rank += is_anchor(cs, th, n, T, t) ? 1 : 0;
             const int p = pair_off[n] + rank;
@@ -181,7 +149,6 @@ __global__ __launch_bounds__(256) void emit_needed_sources_kernel(const float* _
                                                                   int32_t* __restrict__ pair_frame,
                                                                   int32_t* __restrict__ src_row, int32_t* __restrict__ tgt,
                                                                   int32_t* __restrict__ out_idx) {
-    __shared__ int lds4[4];
     const int a = blockIdx.x;
     int carry = frame_off[a];
     for (int n0 = 0; n0 < N; n0 += 256) {
@@ -189,14 +156,14 @@ __global__ __launch_bounds__(256) void emit_needed_sources_kernel(const float* _
         const bool anchor = n < N && is_anchor(cs, anchor_th, n, T, a);
         const int weight = anchor ? need_w[n] : 0;
         int total;
-        const int incl = block_scan_incl(weight, lds4, &total);
+        const int excl = block_scan_excl<4>(weight, total);
         if (anchor) {
             int rank = 0;
             for (int t = 0; t < a; ++t) rank += is_anchor(cs, anchor_th, n, T, t) ? 1 : 0;
             const int p = pair_off[n] + rank;
             pair_frame[p] = a;
             if (weight > 0) {
-                int m = carry + incl - weight;  // first source of this pair among the sources sorted by anchor frame
+                int m = carry + excl;  // first source of this pair among the sources sorted by anchor frame
                 for (int t = 0; t < T; ++t) {
                     if (!is_needed(cs[(size_t)n * T + t], anchor_th, cos_th)) continue;
                     src_row[m] = n * T + t;

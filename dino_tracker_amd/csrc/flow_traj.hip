@@ -17,7 +17,7 @@
 // The reference's per-component mask and its one_nan_least pass reduce to one flag per trajectory: the mask only ever shrinks, so
 // a thread stops at its first dead step.
 #include <math.h>
-#include "common.h"
+#include "block_scan.h"
 
 #pragma clang fp contract(off)
 
@@ -119,68 +119,16 @@ __global__ __launch_bounds__(FT_BLOCK) void cycle_mask_kernel(const f2* __restri
     out[at] = (out[at] != 0 && dist(g, c2) < threshold) ? 1 : 0;
 }
 
-// ---- ordered compaction (the count / scan / write pattern of of_prep.hip) -----------------------------------------------------
+// ---- ordered compaction (count, block_offsets_kernel, write at offset + rank: the primitives of block_scan.h) ------------------
 __device__ __forceinline__ bool start_live(const uint8_t* consistent, const uint8_t* visited, int p, int hw) {
     return p < hw && (consistent[p] == 0 || visited[p] == 0);
-}
-
-// block sum of a per-thread flag -> count[blockIdx.x]
-__device__ __forceinline__ void block_count(bool v, int32_t* __restrict__ count) {
-    __shared__ int wsum[FT_BLOCK / WAVE];
-    const int c = __popcll(__ballot(v));
-    if ((threadIdx.x & (WAVE - 1)) == 0) wsum[threadIdx.x / WAVE] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int s = 0;
-        for (int k = 0; k < FT_BLOCK / WAVE; ++k) s += wsum[k];
-        count[blockIdx.x] = s;
-    }
-}
-
-// rank of a set flag among the block's set flags, in thread order; every thread of the block calls it
-__device__ __forceinline__ int block_rank(bool v) {
-    __shared__ int wsum[FT_BLOCK / WAVE];
-    const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
-    const unsigned long long m = __ballot(v);
-    if (lane == 0) wsum[wv] = __popcll(m);
-    __syncthreads();
-    int base = 0;
-    for (int k = 0; k < wv; ++k) base += wsum[k];
-    return base + __popcll(m & ((1ull << lane) - 1ull));
 }
 
 __global__ __launch_bounds__(FT_BLOCK) void start_count_kernel(const uint8_t* __restrict__ consistent,
                                                                const uint8_t* __restrict__ visited, int hw,
                                                                int32_t* __restrict__ count) {
-    block_count(start_live(consistent, visited, blockIdx.x * FT_BLOCK + threadIdx.x, hw), count);
-}
-
-// one block: count[0 .. nblk) -> exclusive offsets in place, *total = their sum
-__global__ __launch_bounds__(FT_BLOCK) void scan_kernel(int32_t* __restrict__ c, int nblk, int32_t* __restrict__ total) {
-    __shared__ int wsum[FT_BLOCK / WAVE];
-    const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
-    int carry = 0;
-    for (int i0 = 0; i0 < nblk; i0 += FT_BLOCK) {
-        const int i = i0 + threadIdx.x;
-        const int v = i < nblk ? c[i] : 0;
-        int x = v;
-#pragma unroll
-        for (int o = 1; o < WAVE; o <<= 1) {
-            const int y = __shfl_up(x, o, WAVE);
-            if (lane >= o) x += y;
-        }
-        __syncthreads();
-        if (lane == WAVE - 1) wsum[wv] = x;
-        __syncthreads();
-        int base = carry, sum = 0;
-        for (int k = 0; k < FT_BLOCK / WAVE; ++k) {
-            if (k < wv) base += wsum[k];
-            sum += wsum[k];
-        }
-        if (i < nblk) c[i] = base + x - v;
-        carry += sum;
-    }
-    if (threadIdx.x == 0) *total = carry;
+    const int c = block_count<FT_BLOCK / WAVE>(start_live(consistent, visited, blockIdx.x * FT_BLOCK + threadIdx.x, hw));
+    if (threadIdx.x == 0) count[blockIdx.x] = c;
 }
 
 __global__ __launch_bounds__(FT_BLOCK) void start_compact_kernel(const uint8_t* __restrict__ consistent,
@@ -188,7 +136,7 @@ __global__ __launch_bounds__(FT_BLOCK) void start_compact_kernel(const uint8_t* 
                                                                  const int32_t* __restrict__ offs, int32_t* __restrict__ pix) {
     const int p = blockIdx.x * FT_BLOCK + threadIdx.x;
     const bool v = start_live(consistent, visited, p, hw);
-    const int r = block_rank(v);
+    const int r = block_rank<FT_BLOCK / WAVE>(v);
     if (v) pix[offs[blockIdx.x] + r] = p;
 }
 
@@ -230,7 +178,8 @@ __global__ __launch_bounds__(FT_BLOCK) void walk_kernel(const f2* __restrict__ f
         }
         len[i] = L;
     }
-    block_count(L >= min_len, keep_count);
+    const int kept = block_count<FT_BLOCK / WAVE>(L >= min_len);
+    if (threadIdx.x == 0) keep_count[blockIdx.x] = kept;
 }
 
 // ---- emit ----------------------------------------------------------------------------------------------------------------------
@@ -247,7 +196,7 @@ __global__ __launch_bounds__(FT_BLOCK) void emit_kernel(const f2* __restrict__ s
     const int i = blockIdx.x * FT_BLOCK + threadIdx.x;
     const int L = i < *n_live ? len[i] : 0;
     const bool keep = L >= min_len;
-    int row = keep_off[blockIdx.x] + block_rank(keep);
+    int row = keep_off[blockIdx.x] + block_rank<FT_BLOCK / WAVE>(keep);
     if (!keep || row >= n_rows) row = -1;
     const f2 nan2 = {NAN, NAN};
     for (int t0 = 0; t0 < T; t0 += FT_CHUNK) {
@@ -362,7 +311,7 @@ extern "C" int dtk_flow_traj_start(const float* fpk, const float* bpk, const uin
     const uint8_t* cons_s = consistent + (size_t)s * hw;
     const uint8_t* vis_s = visited + (size_t)s * hw;
     DTK_LAUNCH("flow_start_count", start_count_kernel, dim3(nblk), dim3(FT_BLOCK), 0, st, cons_s, vis_s, hw, live_off);
-    DTK_LAUNCH("flow_scan", scan_kernel, dim3(1), dim3(FT_BLOCK), 0, st, live_off, nblk, n_live);
+    DTK_LAUNCH("flow_scan", block_offsets_kernel<FT_BLOCK / WAVE>, dim3(1), dim3(FT_BLOCK), 0, st, live_off, nblk, n_live);
     DTK_LAUNCH("flow_start_compact", start_compact_kernel, dim3(nblk), dim3(FT_BLOCK), 0, st, cons_s, vis_s, hw, live_off, pix);
     const f2* fp = reinterpret_cast<const f2*>(fpk);
     const f2* bp = reinterpret_cast<const f2*>(bpk);
@@ -374,7 +323,7 @@ extern "C" int dtk_flow_traj_start(const float* fpk, const float* bpk, const uin
         DTK_LAUNCH("flow_walk", walk_kernel<false>, dim3(nblk), dim3(FT_BLOCK), 0, st, fp, bp, (const f2*)nullptr,
                    (const f2*)nullptr, T, h, w, s, threshold, 0.f, min_trajectory_length, n_live, pix, slab, len, keep_off);
     }
-    DTK_LAUNCH("flow_scan", scan_kernel, dim3(1), dim3(FT_BLOCK), 0, st, keep_off, nblk, n_rows);
+    DTK_LAUNCH("flow_scan", block_offsets_kernel<FT_BLOCK / WAVE>, dim3(1), dim3(FT_BLOCK), 0, st, keep_off, nblk, n_rows);
     return 0;
 }
 

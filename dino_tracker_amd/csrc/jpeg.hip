@@ -21,7 +21,7 @@
 // Huffman tables can express, which the transform never leaves, so the bound holds whatever the coefficient buffer contains), an
 // interval at most 16 * 6 * 1658 bits = 19 896 bytes before stuffing and twice that after it: DTK_JPEG_INTERVAL_BYTES.
 #include <algorithm>
-#include "common.h"
+#include "block_scan.h"
 
 namespace {
 
@@ -225,30 +225,6 @@ __global__ __launch_bounds__(THREADS) void jpeg_transform_kernel(const uint8_t* 
     for (int i = tid; i < nm * 6 * 32; i += THREADS) dst[i] = from[i];
 }
 
-// exclusive scan of one value per thread over the workgroup (every thread calls); ws: WAVES values of LDS
-template <class T>
-__device__ __forceinline__ T block_scan_exclusive(T v, T* ws, T& total) {
-    const int lane = threadIdx.x % WAVE, wave = threadIdx.x / WAVE;
-    T inc = v;
-#pragma unroll
-    for (int d = 1; d < WAVE; d <<= 1) {
-        const T o = __shfl_up(inc, d);
-        if (lane >= d) inc += o;
-    }
-    __syncthreads();   // ws may still be read from the previous call
-    if (lane == WAVE - 1) ws[wave] = inc;
-    __syncthreads();
-    T base = 0;
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < WAVES; ++w) {
-        const T s = ws[w];
-        base += w < wave ? s : (T)0;
-        total += s;
-    }
-    return base + inc - v;
-}
-
 // the bits of one block, most significant first, into `buf` from bit `pos` (EMIT), or only their count
 template <bool EMIT>
 struct BitSink {
@@ -315,7 +291,6 @@ __global__ __launch_bounds__(THREADS) void jpeg_code_kernel(const int16_t* __res
     __shared__ __align__(4) int16_t cz[R * 6][CZ_STRIDE];
     __shared__ uint32_t bitbuf[INTERVAL_WORDS];
     __shared__ uint32_t huff[2][HUFF_WORDS];
-    __shared__ int ws[WAVES];
     const int tid = threadIdx.x;
     const size_t f = (size_t)f0 + blockIdx.y;
     const int it = blockIdx.x, m0 = it * R, nm = min(R, mcus - m0), nb = nm * 6;
@@ -333,7 +308,7 @@ __global__ __launch_bounds__(THREADS) void jpeg_code_kernel(const int16_t* __res
     }
     const int len = tid < nb ? code_block<false>(cz[tid], pred, huff[comp], nullptr, 0) : 0;
     int total_bits;
-    const int pos = block_scan_exclusive(len, ws, total_bits);
+    const int pos = block_scan_excl<WAVES>(len, total_bits);
     for (int i = tid; i < total_bits / 32 + 1; i += THREADS) bitbuf[i] = 0u;
     __syncthreads();
     if (tid < nb) code_block<true>(cz[tid], pred, huff[comp], bitbuf, pos);
@@ -350,7 +325,7 @@ __global__ __launch_bounds__(THREADS) void jpeg_code_kernel(const int16_t* __res
         const unsigned byte = i < nbytes ? (bitbuf[i >> 2] >> (24 - 8 * (i & 3))) & 0xffu : 0u;
         const int ff = byte == 0xffu;
         int chunk;
-        const int o = i + stuffed + block_scan_exclusive(ff, ws, chunk);
+        const int o = i + stuffed + block_scan_excl<WAVES>(ff, chunk);
         if (i < nbytes && o + 1 < SLOT) {
             slot[o] = (uint8_t)byte;
             if (ff) slot[o + 1] = 0;
@@ -365,14 +340,13 @@ __global__ __launch_bounds__(THREADS) void jpeg_code_kernel(const int16_t* __res
 __global__ __launch_bounds__(THREADS) void jpeg_frame_scan_kernel(const uint32_t* __restrict__ ilen, int n_int, int header_bytes,
                                                                   unsigned long long* __restrict__ ioff,
                                                                   unsigned long long* __restrict__ flen) {
-    __shared__ unsigned long long ws[WAVES];
     const size_t f = blockIdx.x;
     unsigned long long at = (unsigned long long)header_bytes;
     for (int i0 = 0; i0 < n_int; i0 += THREADS) {
         const int i = i0 + (int)threadIdx.x;
         const unsigned long long mine = i < n_int ? (unsigned long long)ilen[f * n_int + i] + (i > 0 ? 2u : 0u) : 0ull;
         unsigned long long chunk;
-        const unsigned long long o = block_scan_exclusive(mine, ws, chunk);
+        const unsigned long long o = block_scan_excl<WAVES>(mine, chunk);
         if (i < n_int) ioff[f * n_int + i] = at + o;
         at += chunk;
     }
@@ -382,12 +356,11 @@ __global__ __launch_bounds__(THREADS) void jpeg_frame_scan_kernel(const uint32_t
 // one workgroup: offsets[f] = where frame f starts in the stream, offsets[F] = *needed = the stream's length
 __global__ __launch_bounds__(THREADS) void jpeg_offsets_kernel(const unsigned long long* __restrict__ flen, int F,
                                                                long long* __restrict__ offsets, long long* __restrict__ needed) {
-    __shared__ unsigned long long ws[WAVES];
     unsigned long long at = 0;
     for (int f0 = 0; f0 < F; f0 += THREADS) {
         const int f = f0 + (int)threadIdx.x;
         unsigned long long chunk;
-        const unsigned long long o = block_scan_exclusive(f < F ? flen[f] : 0ull, ws, chunk);
+        const unsigned long long o = block_scan_excl<WAVES>(f < F ? flen[f] : 0ull, chunk);
         if (f < F) offsets[f] = (long long)(at + o);
         at += chunk;
     }

@@ -14,7 +14,7 @@
 // (bits(d^2) << 32 | n): d^2 >= 0, so its IEEE bits order like the value and the key orders like (d^2, n).
 #include <math.h>
 #include <algorithm>
-#include "common.h"
+#include "block_scan.h"
 
 namespace {
 
@@ -53,7 +53,6 @@ __global__ __launch_bounds__(OF_BLOCK) void traj_start_fg_kernel(const float* __
 // count[t * nblk + b] = tracked points of frame t among the rows of block b
 __global__ __launch_bounds__(OF_BLOCK) void nn_count_kernel(const float* __restrict__ traj, int N, int T, int nblk,
                                                             int32_t* __restrict__ count) {
-    __shared__ int wsum[OF_BLOCK / WAVE];
     const int b = blockIdx.x, t = blockIdx.y;
     const long long n = (long long)b * OF_BLOCK + threadIdx.x;
     bool v = false;
@@ -61,64 +60,22 @@ __global__ __launch_bounds__(OF_BLOCK) void nn_count_kernel(const float* __restr
         const f2 p = reinterpret_cast<const f2*>(traj)[(size_t)n * T + t];
         v = tracked(p.x, p.y);
     }
-    const int c = __popcll(__ballot(v));
-    if ((threadIdx.x & (WAVE - 1)) == 0) wsum[threadIdx.x / WAVE] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int s = 0;
-        for (int w = 0; w < OF_BLOCK / WAVE; ++w) s += wsum[w];
-        count[(size_t)t * nblk + b] = s;
-    }
-}
-
-// one block per frame: count[t][*] -> exclusive offsets in place, total[t]
-__global__ __launch_bounds__(OF_BLOCK) void nn_scan_kernel(int32_t* __restrict__ count, int nblk, int32_t* __restrict__ total) {
-    __shared__ int wsum[OF_BLOCK / WAVE];
-    int32_t* c = count + (size_t)blockIdx.x * nblk;
-    const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x / WAVE;
-    int carry = 0;
-    for (int i0 = 0; i0 < nblk; i0 += OF_BLOCK) {
-        const int i = i0 + threadIdx.x;
-        const int v = i < nblk ? c[i] : 0;
-        int x = v;
-#pragma unroll
-        for (int o = 1; o < WAVE; o <<= 1) {
-            const int y = __shfl_up(x, o, WAVE);
-            if (lane >= o) x += y;
-        }
-        __syncthreads();
-        if (lane == WAVE - 1) wsum[w] = x;
-        __syncthreads();
-        int base = carry, sum = 0;
-        for (int k = 0; k < OF_BLOCK / WAVE; ++k) {
-            if (k < w) base += wsum[k];
-            sum += wsum[k];
-        }
-        if (i < nblk) c[i] = base + x - v;
-        carry += sum;
-    }
-    if (threadIdx.x == 0) total[blockIdx.x] = carry;
+    const int c = block_count<OF_BLOCK / WAVE>(v);
+    if (threadIdx.x == 0) count[(size_t)t * nblk + b] = c;
 }
 
 // frame t's tracked points in row order: pts[t * N + k] = (x, y), ids[t * N + k] = n
 __global__ __launch_bounds__(OF_BLOCK) void nn_compact_kernel(const float* __restrict__ traj, int N, int T, int nblk,
                                                               const int32_t* __restrict__ offs, f2* __restrict__ pts,
                                                               int32_t* __restrict__ ids) {
-    __shared__ int wsum[OF_BLOCK / WAVE];
     const int b = blockIdx.x, t = blockIdx.y;
-    const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x / WAVE;
     const long long n = (long long)b * OF_BLOCK + threadIdx.x;
     f2 p = {NAN, NAN};
     if (n < N) p = reinterpret_cast<const f2*>(traj)[(size_t)n * T + t];
     const bool v = tracked(p.x, p.y);
-    const unsigned long long m = __ballot(v);
-    const int below = __popcll(m & ((1ull << lane) - 1ull));
-    if (lane == 0) wsum[w] = __popcll(m);
-    __syncthreads();
-    int base = offs[(size_t)t * nblk + b];
-    for (int k = 0; k < w; ++k) base += wsum[k];
+    const int rank = block_rank<OF_BLOCK / WAVE>(v);
     if (v) {
-        const size_t at = (size_t)t * N + base + below;
+        const size_t at = (size_t)t * N + offs[(size_t)t * nblk + b] + rank;
         pts[at] = p;
         ids[at] = (int32_t)n;
     }
@@ -317,7 +274,8 @@ extern "C" int dtk_nearest_traj(const float* traj, int N, int T, int gh, int gw,
     if (N > 0) {
         const int nblk = dtk_cdiv(N, OF_BLOCK);
         DTK_LAUNCH("nn_count", nn_count_kernel, dim3(nblk, T), dim3(OF_BLOCK), 0, st, traj, N, T, nblk, count);
-        DTK_LAUNCH("nn_scan", nn_scan_kernel, dim3(T), dim3(OF_BLOCK), 0, st, count, nblk, total);
+        // one block per frame: count[t][*] -> exclusive offsets in place, total[t]
+        DTK_LAUNCH("nn_scan", block_offsets_kernel<OF_BLOCK / WAVE>, dim3(T), dim3(OF_BLOCK), 0, st, count, nblk, total);
         DTK_LAUNCH("nn_compact", nn_compact_kernel, dim3(nblk, T), dim3(OF_BLOCK), 0, st, traj, N, T, nblk, count, pts, ids);
         // candidate splits: ~16 blocks per CU over (grid blocks x frames), never more than the tiles of a full frame
         const int gblk = dtk_cdiv(G, OF_BLOCK * NN_PTS);

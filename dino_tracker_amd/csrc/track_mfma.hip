@@ -23,7 +23,7 @@
 #include <limits.h>
 #include <stdlib.h>
 #include <type_traits>
-#include "common.h"
+#include "block_scan.h"
 #include "head_common.h"
 
 int dtk_track_exact(const dtk_geom* g, const float* feat, const float* norms, const float* head, const float* emb,
@@ -457,7 +457,7 @@ __global__ __launch_bounds__(256) void select_kernel(dtk_geom g, const TileRec* 
         }
         if (cnt > 2) overflow = true;
     }
-    int total = ncand;
+    int total = ncand;  // (wave_scan_incl of block_scan.h, kept spelled out: the call changes this kernel's machine code)
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {
         const int y = __shfl_up(total, o, WAVE);
@@ -1440,10 +1440,9 @@ __global__ __launch_bounds__(256) void rescore_kernel(dtk_geom g, const float* _
     }
 }
 
-// ---- exclusive scan of the key histogram (n up to T * HWk): block sums -> scan of block sums -> final -------------
+// ---- exclusive scan of the key histogram (n up to T * HWk): block sums -> scan of block sums (block_offsets_kernel) -> final
 constexpr int SCAN_PER_BLOCK = 1024;
 __global__ __launch_bounds__(256) void scan_blocksum_kernel(const int32_t* __restrict__ in, int32_t* __restrict__ bsum, int n) {
-    __shared__ int red[4];
     const int base = blockIdx.x * SCAN_PER_BLOCK;
     int s = 0;
 #pragma unroll
@@ -1451,52 +1450,19 @@ __global__ __launch_bounds__(256) void scan_blocksum_kernel(const int32_t* __res
         const int idx = base + j * 256 + threadIdx.x;
         s += idx < n ? in[idx] : 0;
     }
-    s = wave_sum_i(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) bsum[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
-}
-__device__ __forceinline__ int block_incl_scan(int v, int* lds4, int* total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int y = __shfl_up(x, o, WAVE);
-        if (lane >= o) x += y;
-    }
-    __syncthreads();
-    if (lane == 63) lds4[w] = x;
-    __syncthreads();
-    int base = 0;
-    for (int k = 0; k < w; ++k) base += lds4[k];
-    *total = lds4[0] + lds4[1] + lds4[2] + lds4[3];
-    return x + base;
-}
-__global__ __launch_bounds__(256) void scan_top_kernel(int32_t* __restrict__ bsum, int nb, int32_t* __restrict__ total_out) {
-    __shared__ int lds4[4];
-    int carry = 0;
-    for (int i0 = 0; i0 < nb; i0 += 256) {
-        const int i = i0 + threadIdx.x;
-        const int v = i < nb ? bsum[i] : 0;
-        int total;
-        const int incl = block_incl_scan(v, lds4, &total);
-        if (i < nb) bsum[i] = carry + incl - v;
-        carry += total;
-    }
-    if (threadIdx.x == 0) *total_out = carry;
+    s = block_sum_i<4>(s);
+    if (threadIdx.x == 0) bsum[blockIdx.x] = s;
 }
 __global__ __launch_bounds__(256) void scan_final_kernel(const int32_t* __restrict__ in, const int32_t* __restrict__ boff,
                                                          int32_t* __restrict__ out, int n) {
-    __shared__ int lds4[4];
     const int base = blockIdx.x * SCAN_PER_BLOCK;
     int carry = boff[blockIdx.x];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int idx = base + j * 256 + threadIdx.x;
-        const int v = idx < n ? in[idx] : 0;
         int total;
-        const int incl = block_incl_scan(v, lds4, &total);
-        if (idx < n) out[idx] = carry + incl - v;
+        const int excl = block_scan_excl<4>(idx < n ? in[idx] : 0, total);
+        if (idx < n) out[idx] = carry + excl;
         carry += total;
     }
 }
@@ -2367,7 +2333,7 @@ int mfma_phase(const dtk_geom* g, const MfmaLayout& L, unsigned char* ws, const 
                    row_table ? reinterpret_cast<const float*>(ws + L.rown) : (const float*)nullptr);
         if (arg_cell) continue;  // arg-max only: no window refinement
         DTK_LAUNCH("key_scan", scan_blocksum_kernel, dim3(L.nblocks), dim3(256), 0, st, hist, bsum, L.nkeys);
-        DTK_LAUNCH("key_scan", scan_top_kernel, dim3(1), dim3(256), 0, st, bsum, L.nblocks, nvalid);
+        DTK_LAUNCH("key_scan", block_offsets_kernel<4>, dim3(1), dim3(256), 0, st, bsum, L.nblocks, nvalid);
         DTK_LAUNCH("key_scan", scan_final_kernel, dim3(L.nblocks), dim3(256), 0, st, hist, bsum, koff, L.nkeys);
         DTK_LAUNCH("key_scatter", scatter_kernel, dim3(dtk_cdiv(scnt, 256)), dim3(256), 0, st, *g, in.tgt, kstar, koff, cursor,
                    perm, L.HWk, (int)s0, scnt);

@@ -147,6 +147,27 @@ def test_edge_cases():
         split_trajectories_fg_bg(outside, masks, DEV)
 
 
+def test_nearest_crosses_scan_chunks():
+    """66 049 rows are 259 blocks of 256 per frame, so the per-frame offsets scan (nn_scan) carries past its first 256 counts;
+    the last tracked row of frame 1 is the only row of the last, partial block.  Tracked rows sit on distinct integer pixels:
+    fp32 squared distances are exact, and ties go to the lowest row (test_edge_cases)."""
+    from dino_tracker_amd.of_preprocessing import nearest_trajectories
+    N, hw, stride = 257 * 257, 32, 7
+    traj = np.full((N, 2, 2), np.nan, dtype=np.float32)
+    want = []
+    grid = D.grid_points(hw, hw, stride)
+    for t, (rem, mul) in enumerate(((0, 397), (256, 613))):
+        rows = np.nonzero(np.arange(N) % 257 == rem)[0]
+        pix = (np.arange(len(rows)) * mul + 5 * t) % (hw * hw)                      # odd multiplier: distinct pixels
+        assert len(np.unique(pix)) == len(rows) == 257
+        traj[rows, t] = np.stack([pix % hw, pix // hw], axis=1).astype(np.float32)
+        d2 = ((traj[rows, t][None] - grid[:, None]) ** 2).sum(-1, dtype=np.float32)
+        want.append(rows[d2.argmin(axis=1)])                                        # argmin: the first minimum
+    assert bool(np.isfinite(traj[N - 1, 1]).all()) and -(-N // 256) == 259
+    idx = nearest_trajectories(torch.from_numpy(traj), hw, hw, stride, DEV).cpu().numpy()
+    assert np.array_equal(idx, np.stack(want))
+
+
 # ---- headline size: T = 90 at 476 x 854, ~1 M trajectories, against ATen on the GPU ---------------------------------------------
 def synth_headline(N=1_000_000, T=90, h=476, w=854, seed=5):
     g = torch.Generator(device=DEV).manual_seed(seed)
