@@ -151,7 +151,7 @@ def _save(obj, path: str) -> None:
 def run_split(traj_path: str, masks_path: str, fg_path: str, bg_path: str, device="cuda:0"):
     from .train import load_masks
     trajectories = torch.load(traj_path, map_location="cpu")
-    fg, bg = split_trajectories_fg_bg(trajectories, load_masks(masks_path), device)
+    fg, bg = split_trajectories_fg_bg(trajectories, load_masks(masks_path, device=device), device)
     for traj, path in ((fg, fg_path), (bg, bg_path)):
         traj = traj.cpu()
         torch.save(traj, path)
@@ -227,7 +227,7 @@ def run_all(config_path: str, data_path: str, device="cuda:0", make_masks: bool 
     h, w, stride = config["video_resh"], config["video_resw"], config["dino_stride"]
 
     # 1. split the direct-flow-filtered trajectories to fg / bg
-    fg, bg = split_trajectories_fg_bg(torch.load(traj_path, map_location="cpu"), load_masks(masks_path), device)
+    fg, bg = split_trajectories_fg_bg(torch.load(traj_path, map_location="cpu"), load_masks(masks_path, device=device), device)
     for traj, path in ((fg, config["fg_trajectories_file"]), (bg, config["bg_trajectories_file"])):
         _save(traj.cpu(), path)
     del fg, bg

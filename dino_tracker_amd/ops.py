@@ -929,3 +929,71 @@ def jpeg_pixels(coef: torch.Tensor, qtables: torch.Tensor, H: int, W: int, statu
     check(lib().dtk_jpeg_pixels(_p(coef, torch.int16), _p(qtables, torch.uint8), F, H, W, _p(out), _p(status, torch.int32), _p(ws),
                                 _stream()))
     return out
+
+
+# ---- PNG ingest (csrc/inflate.hip): zlib / DEFLATE streams, their Adler-32, the PNG row filters; the chunk parser is png_in's --------
+INFLATE_STREAM_FIELDS = 4
+(INFLATE_S_HEADER, INFLATE_S_BTYPE, INFLATE_S_STORED, INFLATE_S_TABLE, INFLATE_S_CODE, INFLATE_S_DISTANCE, INFLATE_S_OVERRUN,
+ INFLATE_S_LENGTH, INFLATE_S_ADLER, INFLATE_S_STREAM) = (1 << k for k in range(10))
+PNG_S_FILTER = 1024
+
+
+def _inflate_streams(streams):
+    import numpy as np
+    tab = np.ascontiguousarray(np.asarray(streams, dtype=np.int64))
+    if tab.ndim != 2 or tab.shape[1] != INFLATE_STREAM_FIELDS or tab.shape[0] < 1:
+        raise RuntimeError(f"dino_tracker_amd: streams must be int64 [S, {INFLATE_STREAM_FIELDS}] with S >= 1, got {tab.shape}")
+    return tab
+
+
+def inflate(stream: torch.Tensor, streams, out_bytes: int, wrapper: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
+    """dtk_inflate: stream uint8 [bytes] (device), streams int64 [S, 4] (a HOST array: byte offset in `stream`, byte length, byte
+    offset in the output, expected output bytes -- checked on the host, uploaded here) -> (uint8 [out_bytes], int32 status [S]).
+    wrapper: zlib streams (header and Adler-32 trailer; compare it with `adler32`), else raw DEFLATE."""
+    tab = _inflate_streams(streams)
+    if stream.dim() != 1 or stream.numel() == 0:
+        raise RuntimeError(f"dino_tracker_amd: stream must be uint8 [bytes], got {tuple(stream.shape)}")
+    dev = stream.device
+    out = torch.empty(max(1, int(out_bytes)), dtype=torch.uint8, device=dev)
+    status = torch.empty(tab.shape[0], dtype=torch.int32, device=dev)
+    tab_dev = torch.from_numpy(tab).to(dev)
+    check(lib().dtk_inflate(_p(stream, torch.uint8), int(stream.numel()), _p(tab_dev), tab.ctypes.data, int(tab.shape[0]),
+                            1 if wrapper else 0, _p(out), int(out.numel()), _p(status), _stream()))
+    return out, status
+
+
+def adler32(stream: torch.Tensor, streams, out: torch.Tensor, status: torch.Tensor) -> torch.Tensor:
+    """dtk_adler32: ORs INFLATE_S_ADLER into status[s] where the Adler-32 of stream s's output range differs from the big-endian value
+    in the stream's last four bytes; streams whose status is already set are skipped."""
+    tab = _inflate_streams(streams)
+    if tuple(status.shape) != (tab.shape[0],):
+        raise RuntimeError(f"dino_tracker_amd: status must be int32 [{tab.shape[0]}], got {tuple(status.shape)}")
+    tab_dev = torch.from_numpy(tab).to(stream.device)
+    check(lib().dtk_adler32(_p(stream, torch.uint8), int(stream.numel()), _p(tab_dev), tab.ctypes.data, int(tab.shape[0]),
+                            _p(out, torch.uint8), int(out.numel()), _p(status, torch.int32), _stream()))
+    return status
+
+
+def png_unfilter_workspace_bytes(F: int, H: int, W: int, bpp: int) -> int:
+    """dtk_png_unfilter_workspace_bytes: device bytes dtk_png_unfilter needs (0 for sizes it refuses)."""
+    return int(lib().dtk_png_unfilter_workspace_bytes(int(F), int(H), int(W), int(bpp)))
+
+
+def png_unfilter(raw: torch.Tensor, F: int, H: int, W: int, bpp: int, status: torch.Tensor,
+                 lut: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dtk_png_unfilter: raw uint8 [F * H * (1 + W * bpp)] (filter byte + scanline per row) -> uint8 [F, H, W, bpp].  status int32
+    [F] receives PNG_S_FILTER for frames with a filter byte above 4 (it is not zeroed).  lut uint8 [F, 256] (bpp = 1): the output is
+    lut[f][value]."""
+    F, H, W, bpp = int(F), int(H), int(W), int(bpp)
+    if raw.numel() < F * H * (1 + W * bpp) or F < 1:
+        raise RuntimeError(f"dino_tracker_amd: raw must hold {F} x {H} x (1 + {W} x {bpp}) bytes, got {raw.numel()}")
+    if tuple(status.shape) != (F,):
+        raise RuntimeError(f"dino_tracker_amd: status must be int32 [{F}], got {tuple(status.shape)}")
+    if lut is not None and tuple(lut.shape) != (F, 256):
+        raise RuntimeError(f"dino_tracker_amd: lut must be uint8 [{F}, 256], got {tuple(lut.shape)}")
+    dev = raw.device
+    ws = torch.empty(png_unfilter_workspace_bytes(F, H, W, bpp), dtype=torch.uint8, device=dev)
+    out = torch.empty((F, H, W, bpp), dtype=torch.uint8, device=dev)
+    check(lib().dtk_png_unfilter(_p(raw, torch.uint8), F, H, W, bpp, _p(lut, torch.uint8), _p(out), _p(status, torch.int32), _p(ws),
+                                 _stream()))
+    return out

@@ -29,14 +29,26 @@ from .trainer import make_trainer
 from .utils import add_config_paths
 
 
-def load_masks(masks_path, h_resize=476, w_resize=854) -> torch.Tensor:
-    """preprocessing/split_trajectories_to_fg_bg.py:38-52: the mask files as greyscale, nearest-resized -> [T, h, w] uint8."""
-    from PIL import Image
+def load_masks(masks_path, h_resize=476, w_resize=854, device=None) -> torch.Tensor:
+    """preprocessing/split_trajectories_to_fg_bg.py:38-52: the mask files as greyscale, nearest-resized -> [T, h, w] uint8.
+    With a CUDA `device` the result lives there, and a folder of PNG files that are all grey or all palette images of one size
+    is decoded there from its compressed bytes (png_in: palette indices become grey through Pillow's own convert("L") table; the
+    DTK_PNG_DECODE switch of video_io applies); the same `interpolate` then runs on the device tensor.  The same bits either way."""
     files = sorted(list(Path(masks_path).glob("*.jpg")) + list(Path(masks_path).glob("*.png")))
-    masks = torch.from_numpy(np.stack([np.array(Image.open(f).convert("L")) for f in files])).unsqueeze(1)
+    masks = None
+    if device is not None and torch.device(device).type == "cuda":
+        from .video_io import decode_png_device
+        masks = decode_png_device(files, torch.device(device), modes=("L", "P"), palette="L")
+    on_host = masks is None
+    if on_host:
+        from PIL import Image
+        masks = torch.from_numpy(np.stack([np.array(Image.open(f).convert("L")) for f in files])).unsqueeze(1)
+    else:
+        masks = masks.permute(0, 3, 1, 2)
     h_resize = masks.shape[2] if h_resize is None else h_resize
     w_resize = masks.shape[3] if w_resize is None else w_resize
-    return torch.nn.functional.interpolate(masks, size=(h_resize, w_resize), mode="nearest")[:, 0]
+    masks = torch.nn.functional.interpolate(masks, size=(h_resize, w_resize), mode="nearest")[:, 0]
+    return masks.to(device) if on_host and device is not None else masks
 
 
 def load_video(video_folder, resize=None, device=None) -> torch.Tensor:
@@ -79,7 +91,7 @@ class StandaloneBase:
         self.of_loss_fn = torch.nn.HuberLoss(delta=1 / 32, reduction="none")
 
     def load_fg_masks(self):
-        self.fg_masks = load_masks(self.fg_masks_path, h_resize=self.config["video_resh"]).to(self.device)
+        self.fg_masks = load_masks(self.fg_masks_path, h_resize=self.config["video_resh"], device=self.device)
 
     def load_dino_best_buddies(self):
         self.dino_bb_pairs = torch.load(self.dino_bb_path, map_location=self.device)

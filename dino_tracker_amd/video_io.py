@@ -1,5 +1,6 @@
 """Video ingest on the device: frames are decoded -- baseline 4:2:0 JPEG folders by libdtk (video_in.py, csrc/jpeg_decode.hip:
-the compressed bytes go up), everything else by Pillow on the host and uploaded once as uint8 -- and LANCZOS-resized by libdtk
+the compressed bytes go up), 8-bit grey or RGB PNG folders by libdtk as well when DTK_PNG_DECODE selects it (png_in.py,
+csrc/inflate.hip), everything else by Pillow on the host and uploaded once as uint8 -- and LANCZOS-resized by libdtk
 (csrc/resize.hip) with Pillow's own 8-bit arithmetic, so the result is bit-equal to `Image.resize(..., Image.LANCZOS)` followed by
 `ToTensor` -- what data/data_utils.py:79-104 (`load_video`) and :47-52 (`resize_tensor_frames_lanczos`) compute on the CPU.
 
@@ -171,12 +172,35 @@ def _decode_jpeg_device(files, device: torch.device) -> Optional[torch.Tensor]:
     return video_in.decode_planned(pinned, views, plan, device)
 
 
+# What DTK_PNG_DECODE=auto selects.  The project's bar for ingest: the device path only where it is not slower than the host path beyond
+# the host path's own spread, at every size and compression level measured (docs/MEASUREMENTS.md "PNG decode").
+PNG_AUTO_USES_DEVICE = False
+
+
+def decode_png_device(files, device: torch.device, modes=("RGB", "L"), palette: str = "index") -> Optional[torch.Tensor]:
+    """uint8 [T, H, W, C] on the device when every file is a PNG the device decodes (png_in.parse_png), all are of one size and of
+    one colour type among `modes`, else None: the routing is decided from the chunk headers, before anything is uploaded.
+    DTK_PNG_DECODE = host | device | auto (the default): `host` keeps Pillow for everything, `device` takes the device decoder for
+    every eligible folder, `auto` does what PNG_AUTO_USES_DEVICE says."""
+    mode = os.environ.get("DTK_PNG_DECODE", "auto")
+    if mode not in ("auto", "device", "host"):
+        raise ValueError(f"DTK_PNG_DECODE must be auto, device or host, got {mode!r}")
+    if mode == "host" or (mode == "auto" and not PNG_AUTO_USES_DEVICE) or not files or any(Path(f).suffix != ".png" for f in files):
+        return None
+    from . import png_in
+    pinned, plan, datas, _ = png_in.read_pinned(files)
+    if plan is None or plan.mode not in modes:
+        return None
+    return png_in.decode_planned(pinned, plan, datas, device, palette=palette)
+
+
 def load_video(video_folder, resize=None, num_frames: Optional[int] = None, device="cuda:0") -> torch.Tensor:
     """data/data_utils.py:79-104 with the resize on the device: the frames of `video_folder` in file order (the first
     `num_frames`) as uint8 on the device, LANCZOS-resized to `resize` = (h, w) and converted as ToTensor does -> float32
     [T, C, h, w] on `device`, bit-equal to the host path.  A folder of baseline 4:2:0 JPEG files of one size is decoded on the device
-    from its compressed bytes (a frame whose stream is damaged is decoded by Pillow instead); other frames are decoded by Pillow on
-    the host and uploaded once.  Frames that are not all RGB or all L of one size take the host path (train.load_video) and are
+    from its compressed bytes (a frame whose stream is damaged is decoded by Pillow instead), and so is a folder of 8-bit grey or RGB
+    PNG files of one size when DTK_PNG_DECODE selects the device (decode_png_device; palette, 16-bit, alpha and interlaced files and
+    mixed .jpg / .png folders never do); other frames are decoded by Pillow on the host and uploaded once.  Frames that are not all RGB or all L of one size take the host path (train.load_video) and are
     uploaded afterwards."""
     device = torch.device(device)
     if device.type != "cuda":
@@ -186,6 +210,8 @@ def load_video(video_folder, resize=None, num_frames: Optional[int] = None, devi
     if not files:
         raise RuntimeError(f"dino_tracker_amd: no *.jpg / *.png frames in {video_folder}")
     frames = _decode_jpeg_device(files, device)
+    if frames is None:
+        frames = decode_png_device(files, device)
     if frames is not None:
         h, w = (int(resize[0]), int(resize[1])) if resize is not None else (int(frames.shape[1]), int(frames.shape[2]))
         return resize_lanczos(frames, h, w, out="f32")

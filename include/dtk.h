@@ -990,6 +990,55 @@ int dtk_jpeg_decode_coefficients(const uint8_t* stream, int64_t stream_bytes, co
 int dtk_jpeg_pixels(const int16_t* coef, const uint8_t* qtables, int32_t F, int32_t H, int32_t W, uint8_t* out, int32_t* status,
                     void* workspace, void* stream);
 
+/* ---- Video and mask ingest: PNG DECODING (docs/PNG_DECODE.md): zlib / DEFLATE streams, their Adler-32, the PNG row filters.  The
+ * file is the CALLER's to parse (dino_tracker_amd/png_in.py: signature, IHDR, PLTE, the IDAT payloads joined into one stream per
+ * frame); the library sees byte streams and raw scanlines.  Everything is exact: the format is lossless. ------------------------------
+ * dtk_inflate: n_streams independent zlib (RFC 1950, wrapper = 1: two header bytes, DEFLATE data, the Adler-32 trailer) or raw
+ *   DEFLATE (RFC 1951, wrapper = 0) streams: stored, fixed and dynamic blocks, any number of them, the 32 KiB window.  in [in_bytes]
+ *   (device).  streams int64 [n_streams][DTK_INFLATE_STREAM_FIELDS] = byte offset in `in`, byte length (<= 2^28), byte offset in `out`,
+ *   EXPECTED output bytes (<= 2^30; a PNG frame: H (1 + W bpp)).  The table is passed twice: `streams` on the device (read by the
+ *   kernel) and `streams_host`, the same values in host memory, which are checked BEFORE anything is launched (the call never waits for
+ *   the device).  The kernel repeats the range check on its own copy: an entry that does not fit sets DTK_INFLATE_S_STREAM and decodes
+ *   nothing.  out [out_bytes] uint8.  status int32 [n_streams]: zeroed, then the stream's DTK_INFLATE_S_* bits.  A stream stops at its
+ *   FIRST fault; what it had decoded stays and the rest of its output range is written as zeros, so every byte of every range is
+ *   written.  With wrapper = 1 the stream must hold at least four bytes after the final block; they are compared by dtk_adler32.
+ *   The kernel is memory-safe and terminates for any input bytes: reads are bounded by the stream's end, writes by its output range,
+ *   and every loop iteration consumes at least one bit or produces at least one byte.
+ * dtk_adler32: the Adler-32 (s1 = 1 + sum d[i], s2 = N + sum (N - i) d[i], both mod 65521, from block sums) of every stream's output
+ *   range against the big-endian value in the stream's LAST four bytes; a mismatch ORs DTK_INFLATE_S_ADLER into status[s].  A stream
+ *   whose status is already non-zero is skipped (its output is not what the trailer describes); status is NOT zeroed.  Same tables.
+ * dtk_png_unfilter: raw [F][H][1 + W bpp] (filter byte + scanline, what the zlib stream of an 8-bit non-interlaced PNG holds), bpp = 1
+ *   (grey or palette index) or 3 (RGB) -> out uint8 [F][H][W][bpp].  Filters 0 .. 4 (None, Sub, Up, Average, Paeth) as the PNG
+ *   specification defines them: arithmetic mod 256 on RECONSTRUCTED bytes, Average = floor((left + up) / 2), Paeth ties in the order
+ *   left, up, up-left; bytes outside the image are 0.  A filter byte > 4 ORs DTK_PNG_S_FILTER into status[f] (int32 [F], NOT zeroed:
+ *   it continues dtk_inflate's) and the row is taken as filter 0.  lut (may be null; bpp = 1 only) uint8 [F][256]: out = lut[f][value]
+ *   -- a palette's grey levels -- while the filters run on the untranslated bytes.  workspace:
+ *   dtk_png_unfilter_workspace_bytes(F, H, W, bpp) bytes, 256-byte aligned (one packed row per frame).
+ * No host synchronisation inside.  Refused with DTK_E_INVALID before anything is launched: null pointers, in_bytes, out_bytes or
+ *   n_streams < 1, wrapper other than 0 / 1, a streams_host entry outside the buffers, output ranges that overlap; F < 1, H or W < 1
+ *   or > 65535, bpp other than 1 / 3, lut with bpp = 3; dtk_png_unfilter_workspace_bytes returns 0 for such sizes. */
+#define DTK_INFLATE_STREAM_FIELDS 4
+#define DTK_INFLATE_S_HEADER 1     /* zlib header: CM != 8, window > 32 K, FCHECK fails, or FDICT set */
+#define DTK_INFLATE_S_BTYPE 2      /* block type 3 */
+#define DTK_INFLATE_S_STORED 4     /* a stored block's LEN != ~NLEN */
+#define DTK_INFLATE_S_TABLE 8      /* HLIT > 286, HDIST > 30; a repeat code with no previous length or beyond the count; an
+                                      over-subscribed code; an incomplete code other than a distance code with a single length-1 entry
+                                      (or none); no end-of-block code */
+#define DTK_INFLATE_S_CODE 16      /* literal/length symbol 286 / 287, distance symbol 30 / 31, or no code matches */
+#define DTK_INFLATE_S_DISTANCE 32  /* a back-reference before the stream's first output byte */
+#define DTK_INFLATE_S_OVERRUN 64   /* input exhausted */
+#define DTK_INFLATE_S_LENGTH 128   /* output would exceed the expected size, or the final block ends short of it */
+#define DTK_INFLATE_S_ADLER 256    /* Adler-32 trailer mismatch (dtk_adler32) */
+#define DTK_INFLATE_S_STREAM 512   /* a stream-table entry outside the buffers */
+#define DTK_PNG_S_FILTER 1024      /* a filter byte > 4 (dtk_png_unfilter) */
+int dtk_inflate(const uint8_t* in, int64_t in_bytes, const int64_t* streams, const int64_t* streams_host, int32_t n_streams,
+                int32_t wrapper, uint8_t* out, int64_t out_bytes, int32_t* status, void* stream);
+int dtk_adler32(const uint8_t* in, int64_t in_bytes, const int64_t* streams, const int64_t* streams_host, int32_t n_streams,
+                const uint8_t* out, int64_t out_bytes, int32_t* status, void* stream);
+size_t dtk_png_unfilter_workspace_bytes(int32_t F, int32_t H, int32_t W, int32_t bpp);
+int dtk_png_unfilter(const uint8_t* raw, int32_t F, int32_t H, int32_t W, int32_t bpp, const uint8_t* lut, uint8_t* out,
+                     int32_t* status, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
