@@ -279,6 +279,15 @@ SIGNATURES = {
     "dtk_adler32": (c_int, [c_void_p, ctypes.c_int64, c_void_p, c_void_p, c_int, c_void_p, ctypes.c_int64, c_void_p, c_void_p]),
     "dtk_png_unfilter_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "dtk_png_unfilter": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dtk_png_filter": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "dtk_deflate_bound": (ctypes.c_int64, [ctypes.c_int64]),
+    "dtk_deflate_workspace_bytes": (c_size_t, [c_void_p, c_int]),
+    "dtk_deflate": (c_int, [c_void_p, ctypes.c_int64, c_void_p, c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p,
+                            c_void_p]),
+    "dtk_crc32": (c_int, [c_void_p, ctypes.c_int64, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "dtk_png_encode_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "dtk_png_encode": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p,
+                               c_void_p]),
 }
 
 _LIB = None

@@ -11,7 +11,7 @@
 //                         memory.  The ring is written out in aligned pieces by all lanes; what lies behind `flushed` is final.
 //                         Dynamic blocks: one lane reads the header and sorts the symbols, all lanes fill the look-ups.
 //   adler32_kernel      : a block per stream: s1 = 1 + sum d[i], s2 = N + sum (N - i) d[i], both mod 65521, from per-thread sums
-//                         over 16-byte groups; compared with the stream's last four bytes.
+//                         over 16-byte groups (adler32_core.h, shared with the encoder); compared with the stream's last four bytes.
 //   png_unfilter_kernel : a wave per frame walks blocks of 64 rows as a skewed wavefront: lane k owns row r0 + k and handles pixel x
 //                         at step x + k; its up bytes are what lane k - 1 made one step earlier (one cross-lane move of the packed
 //                         pixel), its up-left bytes are its own previous up bytes.  Lane 63 leaves its row in the carry row of the
@@ -23,6 +23,7 @@
 #include <algorithm>
 #include <vector>
 #include "common.h"
+#include "adler32_core.h"
 #include "inflate_core.h"
 
 static_assert(INF_S_HEADER == DTK_INFLATE_S_HEADER && INF_S_BTYPE == DTK_INFLATE_S_BTYPE && INF_S_STORED == DTK_INFLATE_S_STORED &&
@@ -264,14 +265,10 @@ __global__ __launch_bounds__(WAVE) void inflate_kernel(const uint8_t* __restrict
 }
 
 // ---- Adler-32 ------------------------------------------------------------------------------------------------------------------
-constexpr int ATHREADS = 256, AGROUP = 16;
-constexpr unsigned ADLER_MOD = 65521u;
-
 // grid (streams).  A stream whose status is already set is left alone: its output is not what the trailer describes.
 __global__ __launch_bounds__(ATHREADS) void adler32_kernel(const uint8_t* __restrict__ in, long long in_bytes,
                                                            const long long* __restrict__ streams, const uint8_t* __restrict__ out_all,
                                                            long long out_bytes, int* __restrict__ status) {
-    __shared__ unsigned long long part[3][ATHREADS / WAVE];
     const int tid = threadIdx.x;
     const long long* sg = streams + (size_t)blockIdx.x * FIELDS;
     const long long off = sg[0], len = sg[1], ooff = sg[2], N = sg[3];
@@ -284,39 +281,11 @@ __global__ __launch_bounds__(ATHREADS) void adler32_kernel(const uint8_t* __rest
         if (tid == 0) atomicOr(&status[blockIdx.x], INF_S_OVERRUN);
         return;
     }
-    const uint8_t* d = out_all + ooff;
-    // a tile of 16 x 256 bytes: thread t reads the bytes tile + 256 j + t, whose weights are N - tile - t - 256 j, so its share is
-    // w * sum d[j] - 256 sum j d[j] with w = (N - tile - t) mod 65521
-    unsigned long long s1 = 0, a = 0, b = 0;
-    for (long long tile = 0; tile < N; tile += (long long)ATHREADS * AGROUP) {
-        unsigned sum = 0, wsum = 0;
-#pragma unroll
-        for (int j = 0; j < AGROUP; ++j) {
-            const long long i = tile + (long long)j * ATHREADS + tid;
-            const unsigned v = i < N ? d[i] : 0u;
-            sum += v;
-            wsum += (unsigned)j * v;
-        }
-        s1 += sum;
-        a = (a + (unsigned long long)((N - tile - tid) % ADLER_MOD + ADLER_MOD) % ADLER_MOD * sum) % ADLER_MOD;
-        b += (unsigned long long)ATHREADS * wsum;
-    }
-    unsigned long long v[3] = {s1 % ADLER_MOD, a, b % ADLER_MOD};
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const int r = wave_sum_i((int)v[k]);   // 64 values below 65521
-        if ((tid & (WAVE - 1)) == 0) part[k][tid / WAVE] = (unsigned long long)r;
-    }
-    __syncthreads();
+    const unsigned value = adler32_block(out_all + ooff, N);   // adler32_core.h: thread 0 holds it
     if (tid == 0) {
-        unsigned long long t[3] = {0, 0, 0};
-        for (int k = 0; k < 3; ++k)
-            for (int w = 0; w < ATHREADS / WAVE; ++w) t[k] += part[k][w];
-        const unsigned c1 = (unsigned)((1 + t[0]) % ADLER_MOD);
-        const unsigned c2 = (unsigned)(((unsigned long long)(N % ADLER_MOD) + t[1] + ADLER_MOD - t[2] % ADLER_MOD) % ADLER_MOD);
         const uint8_t* tr = in + off + len - 4;
         const unsigned want = ((unsigned)tr[0] << 24) | ((unsigned)tr[1] << 16) | ((unsigned)tr[2] << 8) | tr[3];
-        if (((c2 << 16) | c1) != want) atomicOr(&status[blockIdx.x], INF_S_ADLER);
+        if (value != want) atomicOr(&status[blockIdx.x], INF_S_ADLER);
     }
 }
 

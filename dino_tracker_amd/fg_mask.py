@@ -135,8 +135,26 @@ def fg_masks_from_video(video: torch.Tensor, model_name: str = "dinov2_vitl14", 
     return get_fg_mask_from_pca(feats.view(T, h, w, -1), (H, W) if img_size is None else img_size, **kwargs)
 
 
+# What DTK_PNG_ENCODE=auto selects.  The device encoder is opt-in until a change flips this on the strength of
+# docs/MEASUREMENTS.md "PNG encode" (the project's bar: not slower than the host path beyond the host path's own spread).
+PNG_AUTO_USES_DEVICE = False
+
+
+def png_encode_on_device() -> bool:
+    """DTK_PNG_ENCODE = host | device | auto (the default): `host` writes masks through Pillow, `device` through the device PNG
+    encoder (png_out.py), `auto` does what PNG_AUTO_USES_DEVICE says.  Anything else raises."""
+    mode = os.environ.get("DTK_PNG_ENCODE", "auto")
+    if mode not in ("auto", "device", "host"):
+        raise ValueError(f"DTK_PNG_ENCODE must be auto, device or host, got {mode!r}")
+    return mode == "device" or (mode == "auto" and PNG_AUTO_USES_DEVICE)
+
+
 def save_masks(mask: torch.Tensor, mask_path: str) -> str:
-    """mask [T, H, W] uint8 -> mask_path/{idx:05d}.png (the names of data_utils.save_video_frames, lossless)."""
+    """mask [T, H, W] uint8 -> mask_path/{idx:05d}.png (the names of data_utils.save_video_frames, lossless).  Pillow writes them,
+    or the device encoder where DTK_PNG_ENCODE selects it (png_encode_on_device): the same pixels either way."""
+    if png_encode_on_device():
+        from . import png_out
+        return png_out.write_png_frames(mask if mask.is_cuda else mask.numpy(), mask_path)
     from PIL import Image
     os.makedirs(mask_path, exist_ok=True)
     for idx, m in enumerate(mask.cpu().numpy()):

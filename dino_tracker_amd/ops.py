@@ -997,3 +997,114 @@ def png_unfilter(raw: torch.Tensor, F: int, H: int, W: int, bpp: int, status: to
     check(lib().dtk_png_unfilter(_p(raw, torch.uint8), F, H, W, bpp, _p(lut, torch.uint8), _p(out), _p(status, torch.int32), _p(ws),
                                  _stream()))
     return out
+
+
+# ---- PNG output (csrc/deflate.hip): the row filters, DEFLATE / zlib, the CRC-32, whole files; the IHDR is png_out's -----------------
+DEFLATE_SEGMENT = 32768
+DEFLATE_RANGE_FIELDS = 2
+PNG_FILTER_ADAPTIVE = 5
+PNG_FILE_OVERHEAD = 57          # signature + IHDR (33), the IDAT chunk's length, type and CRC (12), IEND (12)
+
+
+def _png_frames(frames: torch.Tensor) -> Tuple[int, int, int, int]:
+    if frames.dim() != 4 or frames.shape[3] not in (1, 3) or frames.numel() == 0:
+        raise RuntimeError(f"dino_tracker_amd: frames must be [F, H, W, 1 or 3] uint8 with F, H, W >= 1, got {tuple(frames.shape)}")
+    return tuple(int(v) for v in frames.shape)
+
+
+def _byte_ranges(ranges):
+    import numpy as np
+    tab = np.ascontiguousarray(np.asarray(ranges, dtype=np.int64))
+    if tab.ndim != 2 or tab.shape[1] != DEFLATE_RANGE_FIELDS or tab.shape[0] < 1:
+        raise RuntimeError(f"dino_tracker_amd: ranges must be int64 [S, {DEFLATE_RANGE_FIELDS}] with S >= 1, got {tab.shape}")
+    return tab
+
+
+def png_filter(frames: torch.Tensor, filter: int = PNG_FILTER_ADAPTIVE) -> torch.Tensor:
+    """dtk_png_filter: frames uint8 [F, H, W, bpp] -> uint8 [F, H, 1 + W * bpp], a filter byte and the filtered scanline per row.
+    filter 0 .. 4 forces one PNG filter, 5 picks per row the one with the smallest sum of |byte as int8| (ties: the lowest number)."""
+    F, H, W, bpp = _png_frames(frames)
+    raw = torch.empty((F, H, 1 + W * bpp), dtype=torch.uint8, device=frames.device)
+    check(lib().dtk_png_filter(_p(frames, torch.uint8), F, H, W, bpp, int(filter), _p(raw), _stream()))
+    return raw
+
+
+def deflate_bound(n: int) -> int:
+    """dtk_deflate_bound: no stream of n input bytes is longer (zlib wrapper included)"""
+    return int(lib().dtk_deflate_bound(int(n)))
+
+
+def deflate(data: torch.Tensor, ranges, wrapper: bool = True, capacity: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """dtk_deflate: data uint8 [bytes] (device), ranges int64 [S, 2] (a HOST array: byte offset and length of every stream's input --
+    checked on the host, uploaded here) -> (uint8 [bytes] -- the S zlib or raw DEFLATE streams one after the other --, int64 [S + 1]
+    offsets, both on the device).  `capacity` is the size of the first output buffer (default: the sum of the bounds, which always
+    suffices); ONE host read-back, the output's length.  When the output does not fit, the call has written nothing and is repeated
+    once with a buffer of exactly that length."""
+    tab = _byte_ranges(ranges)
+    if data.dim() != 1 or data.numel() == 0:
+        raise RuntimeError(f"dino_tracker_amd: data must be uint8 [bytes], got {tuple(data.shape)}")
+    S, dev = int(tab.shape[0]), data.device
+    ws = torch.empty(max(1, int(lib().dtk_deflate_workspace_bytes(tab.ctypes.data, S))), dtype=torch.uint8, device=dev)
+    tab_dev = torch.from_numpy(tab).to(dev)
+    offsets = torch.empty(S + 1, dtype=torch.int64, device=dev)
+    needed = torch.empty(1, dtype=torch.int64, device=dev)
+    cap = sum(deflate_bound(max(0, int(n))) for n in tab[:, 1]) if capacity is None else max(int(capacity), 1)
+    for attempt in range(2):
+        out = torch.empty(cap, dtype=torch.uint8, device=dev)
+        check(lib().dtk_deflate(_p(data, torch.uint8), int(data.numel()), _p(tab_dev), tab.ctypes.data, S, 1 if wrapper else 0, _p(out),
+                                cap, _p(offsets), _p(needed), _p(ws), _stream()))
+        n = int(needed.item())                        # the read-back
+        if n <= cap:
+            return out[:n], offsets
+        cap = n
+    raise RuntimeError(f"dino_tracker_amd: deflate needs {n} bytes after a retry with as many")
+
+
+def crc32(data: torch.Tensor, ranges) -> torch.Tensor:
+    """dtk_crc32: the CRC-32 (PNG / zlib) of the byte ranges int64 [S, 2] (a HOST array) of data uint8 [bytes] -> int64 [S] on the
+    device, values 0 .. 2^32 - 1."""
+    tab = _byte_ranges(ranges)
+    if data.dim() != 1 or data.numel() == 0:
+        raise RuntimeError(f"dino_tracker_amd: data must be uint8 [bytes], got {tuple(data.shape)}")
+    S, dev = int(tab.shape[0]), data.device
+    tab_dev = torch.from_numpy(tab).to(dev)
+    out = torch.empty(S, dtype=torch.int32, device=dev)
+    check(lib().dtk_crc32(_p(data, torch.uint8), int(data.numel()), _p(tab_dev), tab.ctypes.data, S, _p(out), _stream()))
+    return out.to(torch.int64) & 0xFFFFFFFF
+
+
+def png_encode_workspace_bytes(F: int, H: int, W: int, bpp: int) -> int:
+    """dtk_png_encode_workspace_bytes: device bytes dtk_png_encode needs (0 for sizes it refuses)."""
+    return int(lib().dtk_png_encode_workspace_bytes(int(F), int(H), int(W), int(bpp)))
+
+
+def png_worst_case_bytes(F: int, H: int, W: int, bpp: int) -> int:
+    """No F files are longer: the framing and the bound of a frame's raw scanlines."""
+    return F * (PNG_FILE_OVERHEAD + deflate_bound(H * (1 + W * bpp)))
+
+
+def png_encode(frames: torch.Tensor, header: torch.Tensor, filter: int = PNG_FILTER_ADAPTIVE,
+               capacity: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """dtk_png_encode: frames uint8 [F, H, W, bpp], header uint8 [33] (signature + IHDR) -> (uint8 [bytes] -- the F files one after
+    the other --, int64 [F + 1] offsets, both on the device).  The capacity policy is jpeg_encode's: `capacity` sizes the first output
+    buffer (default: the worst case), ONE host read-back, and one retry with exactly the needed size when it was short."""
+    F, H, W, bpp = _png_frames(frames)
+    if tuple(header.shape) != (33,):
+        raise RuntimeError(f"dino_tracker_amd: header must be uint8 [33] (signature and IHDR chunk), got {tuple(header.shape)}")
+    dev = frames.device
+    size = png_encode_workspace_bytes(F, H, W, bpp)
+    if size == 0:
+        raise RuntimeError(f"dino_tracker_amd: png_encode cannot take {F} frames of {H} x {W} x {bpp}")
+    ws = torch.empty(size, dtype=torch.uint8, device=dev)
+    offsets = torch.empty(F + 1, dtype=torch.int64, device=dev)
+    needed = torch.empty(1, dtype=torch.int64, device=dev)
+    cap = png_worst_case_bytes(F, H, W, bpp) if capacity is None else max(int(capacity), 1)
+    for attempt in range(2):
+        out = torch.empty(cap, dtype=torch.uint8, device=dev)
+        check(lib().dtk_png_encode(_p(frames, torch.uint8), F, H, W, bpp, int(filter), _p(header, torch.uint8), _p(out), cap, _p(offsets),
+                                   _p(needed), _p(ws), _stream()))
+        n = int(needed.item())                        # the read-back
+        if n <= cap:
+            return out[:n], offsets
+        cap = n
+    raise RuntimeError(f"dino_tracker_amd: png_encode needs {n} bytes after a retry with as many")

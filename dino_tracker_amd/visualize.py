@@ -448,13 +448,18 @@ def save_video(video, path: str, fps: int = 10, container: Optional[str] = None,
     """Writes [T, H, W, 3] uint8.  container None: an mp4 through imageio when that imports; otherwise PNG frames 00000.png ... in a
     folder named like the file without its extension.  container "avi": <path without extension>.avi, a Motion-JPEG AVI, and "jpg":
     a folder of 00000.jpg ... named like the file without its extension -- both through the device JPEG encoder (video_out.py) at
-    `quality`; a device tensor is encoded where it is, without a trip to the host.  Returns what it wrote and says so."""
+    `quality`.  container "png": a folder of 00000.png ... through the device PNG encoder (png_out.py), lossless.  A device tensor
+    is encoded where it is, without a trip to the host.  Returns what it wrote and says so."""
     if container is not None:
         from . import video_out
-        if container not in ("avi", "jpg"):
-            raise ValueError(f"save_video: container must be None, 'avi' or 'jpg', got {container!r}")
+        if container not in ("avi", "jpg", "png"):
+            raise ValueError(f"save_video: container must be None, 'avi', 'jpg' or 'png', got {container!r}")
         stem, frames = os.path.splitext(path)[0], len(video)
-        if container == "avi":
+        if container == "png":
+            from . import png_out
+            written = png_out.write_png_frames(video, stem)
+            print(f"save_video: wrote {frames} PNG frames (device encoder, lossless) to {written}/")
+        elif container == "avi":
             written = video_out.write_mjpeg_avi(video, stem + ".avi", fps=fps, quality=quality)
             print(f"save_video: wrote {written} (Motion-JPEG avi, {frames} frames, {fps} fps, quality {quality}, "
                   f"{os.path.getsize(written)} bytes)")
@@ -496,9 +501,9 @@ def _container_args(args) -> dict:
 
 
 def _add_container_flags(p: argparse.ArgumentParser) -> None:
-    p.add_argument("--container", choices=("auto", "avi", "jpg"), default="auto",
-                   help="auto: mp4 through imageio, PNG frames without it; avi: Motion-JPEG AVI and jpg: a folder of JPEG frames, "
-                        "both encoded on the device")
+    p.add_argument("--container", choices=("auto", "avi", "jpg", "png"), default="auto",
+                   help="auto: mp4 through imageio, PNG frames without it; avi: Motion-JPEG AVI, jpg: a folder of JPEG frames and "
+                        "png: a folder of PNG frames (lossless), all three encoded on the device")
     p.add_argument("--quality", type=int, default=90, help="JPEG quality 1 .. 100 of --container avi / jpg")
 
 

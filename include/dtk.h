@@ -1039,6 +1039,60 @@ size_t dtk_png_unfilter_workspace_bytes(int32_t F, int32_t H, int32_t W, int32_t
 int dtk_png_unfilter(const uint8_t* raw, int32_t F, int32_t H, int32_t W, int32_t bpp, const uint8_t* lut, uint8_t* out,
                      int32_t* status, void* workspace, void* stream);
 
+/* ---- Video and mask output: PNG ENCODING (docs/PNG_ENCODE.md): the PNG row filters, DEFLATE / zlib compression, the CRC-32 and whole
+ * files; the mirror of the section above.  The filter stage, the Adler-32 and the CRC-32 are defined to the bit; the DEFLATE bytes are
+ * a pure function of the input bytes and decode to them, but they are this library's, not zlib's. -----------------------------------
+ * dtk_png_filter: frames uint8 [F][H][W][bpp], bpp = 1 or 3 -> raw [F][H][1 + W bpp], a filter byte and the filtered scanline per
+ *   row: exactly what dtk_png_unfilter reads.  filter = 0 .. 4 (None, Sub, Up, Average, Paeth) forces that filter for every row;
+ *   filter = 5 is adaptive: per row all five are computed and the one whose filtered bytes have the smallest sum of |value as int8|
+ *   is taken, ties to the lowest filter number (the PNG specification's heuristic).  Encoding filters read ORIGINAL pixels: filtered
+ *   = original - predictor mod 256, Average = floor((left + up) / 2), Paeth ties in the order left, up, up-left; bytes outside the
+ *   image are 0.
+ * dtk_deflate: the n_streams byte ranges of in [in_bytes] (ranges int64 [n_streams][DTK_DEFLATE_RANGE_FIELDS] = byte offset, byte
+ *   length 0 .. 2^30) -> n_streams zlib streams (wrapper = 1: 78 01, DEFLATE data, the big-endian Adler-32 of the range) or raw DEFLATE
+ *   streams (wrapper = 0), one after the other in out.  The table is passed twice, as in dtk_inflate: `ranges` on the device, and
+ *   `ranges_host`, the same values in host memory, checked BEFORE anything is launched; the kernels repeat the check on their copy (an
+ *   entry that does not fit is compressed as an empty range).  offsets int64 [n_streams + 1]: stream s is out[offsets[s] ..
+ *   offsets[s + 1]); *needed (int64) = offsets[n_streams].  offsets and *needed are always written.  If *needed > out_capacity NOTHING
+ *   is written to out and the call still returns 0: the caller reads *needed and calls again.  dtk_deflate_bound(n) is the longest
+ *   stream n input bytes can give (n + 5 bytes per segment + 6), at most n + n / 1024 + 64: a capacity of its sum never needs a retry.
+ *   Format: a range is cut into segments of DTK_DEFLATE_SEGMENT bytes (an empty range is one empty segment); one wave compresses a
+ *   segment with no reference across its start, so every distance is <= 32768.  A segment is ONE block -- stored, fixed or dynamic
+ *   Huffman, whichever is shortest by exact count (ties in that order) --; a coded block of a segment that is not the range's last is
+ *   followed by an empty stored block (00 00 FF FF after the padding, zlib's sync flush), so every segment ends on a byte boundary;
+ *   the last segment's block carries BFINAL.  Matches: greedy, lengths 3 .. 258, found among distance 1, two distances the caller
+ *   of the PNG path names (a pixel, a row) and the newest position of an earlier 64-byte tile with the same 3-byte hash.  Dynamic
+ *   codes: lengths limited to 15 (7 for the code-length code), literal/length and code-length codes complete, one distance code of
+ *   length 1 when no match was emitted.
+ *   workspace: dtk_deflate_workspace_bytes(ranges_host, n_streams) bytes, 256-byte aligned: per stream as many segments as the
+ *   LONGEST range has, each a slot of DTK_DEFLATE_SEGMENT + 64 bytes and 4 DTK_DEFLATE_SEGMENT bytes of tokens -- about five times
+ *   the input for ranges of one size.  0 for a null table, n_streams < 1 or a length outside 0 .. 2^30.
+ * dtk_crc32: the CRC-32 of PNG and zlib (polynomial 0xEDB88320 reflected, start value and final xor 0xFFFFFFFF) of n_ranges byte
+ *   ranges of data [data_bytes] -> crc uint32 [n_ranges].  ranges / ranges_host as above (lengths up to 2^40).  Table-driven over
+ *   pieces of 64 bytes, which are combined by multiplication with x^(8 len) mod P.
+ * dtk_png_encode: filter -> deflate -> assembly for frames uint8 [F][H][W][bpp].  header [33] (device): the caller's signature and
+ *   IHDR chunk with its CRC, copied in front of every frame.  Each file is header, ONE IDAT chunk (length, "IDAT", the zlib stream,
+ *   the CRC-32 over type and data) and IEND; the F files lie one after the other in out.  offsets [F + 1], *needed and out_capacity
+ *   as in dtk_deflate; a file is at most 57 + dtk_deflate_bound(H (1 + W bpp)) bytes.  8-bit, non-interlaced, colour type 0 (bpp 1)
+ *   or 2 (bpp 3).  workspace: dtk_png_encode_workspace_bytes(F, H, W, bpp) bytes, 256-byte aligned (the raw scanlines and
+ *   dtk_deflate's workspace for them).
+ * No host synchronisation inside.  Refused with DTK_E_INVALID before anything is launched: null pointers, F < 1, H or W < 1 or > 65535,
+ *   bpp other than 1 / 3, more than 2^30 raw bytes per frame, filter outside 0 .. 5, in_bytes / data_bytes / n_streams / n_ranges < 1,
+ *   wrapper other than 0 / 1, a ranges_host entry outside the buffer; dtk_png_encode_workspace_bytes returns 0 for such sizes. */
+#define DTK_DEFLATE_SEGMENT 32768
+#define DTK_DEFLATE_RANGE_FIELDS 2
+#define DTK_PNG_FILTER_ADAPTIVE 5
+int dtk_png_filter(const uint8_t* frames, int32_t F, int32_t H, int32_t W, int32_t bpp, int32_t filter, uint8_t* raw, void* stream);
+int64_t dtk_deflate_bound(int64_t n);
+size_t dtk_deflate_workspace_bytes(const int64_t* ranges_host, int32_t n_streams);
+int dtk_deflate(const uint8_t* in, int64_t in_bytes, const int64_t* ranges, const int64_t* ranges_host, int32_t n_streams,
+                int32_t wrapper, uint8_t* out, size_t out_capacity, int64_t* offsets, int64_t* needed, void* workspace, void* stream);
+int dtk_crc32(const uint8_t* data, int64_t data_bytes, const int64_t* ranges, const int64_t* ranges_host, int32_t n_ranges,
+              uint32_t* crc, void* stream);
+size_t dtk_png_encode_workspace_bytes(int32_t F, int32_t H, int32_t W, int32_t bpp);
+int dtk_png_encode(const uint8_t* frames, int32_t F, int32_t H, int32_t W, int32_t bpp, int32_t filter, const uint8_t* header,
+                   uint8_t* out, size_t out_capacity, int64_t* offsets, int64_t* needed, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
