@@ -6,7 +6,7 @@
 // What holds whatever the bytes and the tables contain (the tables the library is handed are validated by the caller, but nothing
 // below relies on it):
 //   * every iteration of the block loop advances the coefficient index by at least one or ends the block: at most 64 iterations per
-//     block, so a segment of M MCUs takes at most 64 * 6 * M -- inside the documented bound 8 * bytes + 64 * 6 * M;
+//     block, so a segment of M MCUs of B blocks takes at most 64 * B * M -- inside the documented bound 8 * bytes + 64 * B * M;
 //   * the reader never touches a word beyond the one that holds the last valid bit plus one (jpg_word checks the index): past
 //     the end the window is zero and JPG_S_OVERRUN is set;
 //   * a coefficient index beyond 63 ends the block with JPG_S_INDEX, a window no code matches ends it with JPG_S_CODE;
@@ -27,6 +27,21 @@
 #define JPG_S_LEFTOVER 8  // more than 7 unread bits at the segment's end
 #define JPG_S_RANGE 16    // |coefficient * Q| > 2047 (set by the pixel stage)
 #define JPG_S_SEGMENT 32  // a segment-table entry outside the stream or the frame's MCUs: nothing decoded
+
+// samplings (DTK_JPEG_* in dtk.h) and the MCU schedule that follows from them (docs/JPEG_DECODE.md section 0): the blocks of an MCU
+// in scan order are the luma blocks, row by row, then Cb, then Cr; a single-component scan is not interleaved: one block.
+#define JPG_420 0    // 2x2 1x1 1x1: Y00 Y01 Y10 Y11 Cb Cr, 16 x 16 pixels
+#define JPG_422 1    // 2x1 1x1 1x1: Y0 Y1 Cb Cr, 16 wide x 8 high
+#define JPG_444 2    // 1x1 1x1 1x1: Y Cb Cr, 8 x 8
+#define JPG_GRAY 3   // one component: Y, 8 x 8
+
+JPG_HD constexpr bool jpg_sampling_ok(int s) { return s >= JPG_420 && s <= JPG_GRAY; }
+JPG_HD constexpr int jpg_blocks_per_mcu(int s) { return s == JPG_420 ? 6 : s == JPG_422 ? 4 : s == JPG_444 ? 3 : 1; }
+JPG_HD constexpr int jpg_components(int s) { return s == JPG_GRAY ? 1 : 3; }
+JPG_HD constexpr int jpg_mcu_width(int s) { return s == JPG_420 || s == JPG_422 ? 16 : 8; }
+JPG_HD constexpr int jpg_mcu_height(int s) { return s == JPG_420 ? 16 : 8; }
+// the component of block k (0 <= k < B) of an MCU of B blocks: all but the last two are luma
+JPG_HD constexpr int jpg_block_component(int B, int k) { return B < 3 || k < B - 2 ? 0 : k - (B - 3); }
 
 constexpr int JPG_LOOK_BITS = 9;
 constexpr int JPG_TABLE_BYTES = 272;   // a raw table: 16 counts, then up to 256 symbols in code order
@@ -169,6 +184,21 @@ JPG_HD int jpg_decode_block(JpgBits& b, const JpgHuff& dc, const JpgHuff& ac, in
         k += r;
         if (k > 63) return JPG_S_INDEX;
         out[k++] = (int16_t)jpg_extend(w, len, s);
+    }
+    return 0;
+}
+
+// The blocks of nm whole MCUs of B blocks each, in scan order, from a reader that holds ALL of the segment's bits: block b goes to
+// coef[b * 64 .. b * 64 + 63] (ZEROED by the caller).  tab[2 c], tab[2 c + 1]: component c's DC and AC look-ups; the predictors start
+// at 0.  Stops at the first block that reports a status and returns it.  (The kernel runs the same schedule -- jpg_block_component
+// with a wrapping counter -- around its staging of the bytes.)
+JPG_HD int jpg_decode_mcus(JpgBits& b, const JpgHuff* tab, int B, int nm, int16_t* coef, uint32_t& iters) {
+    int pred[3] = {0, 0, 0}, k = 0;
+    for (long long blk = 0, n = (long long)nm * B; blk < n; ++blk) {
+        const int comp = jpg_block_component(B, k);
+        const int st = jpg_decode_block(b, tab[2 * comp], tab[2 * comp + 1], pred[comp], coef + blk * 64, iters);
+        if (st) return st;
+        if (++k == B) k = 0;
     }
     return 0;
 }

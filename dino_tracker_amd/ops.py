@@ -880,54 +880,76 @@ def jpeg_encode(frames: torch.Tensor, qtables: torch.Tensor, header: torch.Tenso
 JPEG_SEGMENT_FIELDS = 5
 JPEG_HUFF_BYTES = 272
 JPEG_S_CODE, JPEG_S_INDEX, JPEG_S_OVERRUN, JPEG_S_LEFTOVER, JPEG_S_RANGE, JPEG_S_SEGMENT = 1, 2, 4, 8, 16, 32
+# DTK_JPEG_*: the samplings, and per sampling (blocks per MCU, components, MCU height, MCU width)
+JPEG_420, JPEG_422, JPEG_444, JPEG_GRAY = 0, 1, 2, 3
+JPEG_SAMPLING_NAMES = {JPEG_420: "4:2:0", JPEG_422: "4:2:2", JPEG_444: "4:4:4", JPEG_GRAY: "grayscale"}
+_JPEG_GEOMETRY = {JPEG_420: (6, 3, 16, 16), JPEG_422: (4, 3, 8, 16), JPEG_444: (3, 3, 8, 8), JPEG_GRAY: (1, 1, 8, 8)}
 
 
-def jpeg_decode_workspace_bytes(F: int, H: int, W: int) -> int:
-    """dtk_jpeg_decode_workspace_bytes: device bytes dtk_jpeg_pixels needs for F frames of H x W (0 for sizes it refuses)."""
-    return int(lib().dtk_jpeg_decode_workspace_bytes(int(F), int(H), int(W)))
+def jpeg_geometry(sampling: int) -> Tuple[int, int, int, int]:
+    """(blocks per MCU, components, MCU height, MCU width) of a DTK_JPEG_* sampling"""
+    if sampling not in _JPEG_GEOMETRY:
+        raise RuntimeError(f"dino_tracker_amd: sampling must be JPEG_420, JPEG_422, JPEG_444 or JPEG_GRAY (0 .. 3), got {sampling!r}")
+    return _JPEG_GEOMETRY[sampling]
 
 
-def jpeg_decode_coefficients(stream: torch.Tensor, segments, huffman: torch.Tensor, H: int, W: int
+def jpeg_mcus(H: int, W: int, sampling: int = JPEG_420) -> int:
+    _, _, mh, mw = jpeg_geometry(sampling)
+    return ((int(H) + mh - 1) // mh) * ((int(W) + mw - 1) // mw)
+
+
+def jpeg_decode_workspace_bytes(F: int, H: int, W: int, sampling: int = JPEG_420) -> int:
+    """dtk_jpeg_decode_workspace_bytes_sampled: device bytes dtk_jpeg_pixels_sampled needs for F frames of H x W (0 for what it
+    refuses)."""
+    return int(lib().dtk_jpeg_decode_workspace_bytes_sampled(int(sampling), int(F), int(H), int(W)))
+
+
+def jpeg_decode_coefficients(stream: torch.Tensor, segments, huffman: torch.Tensor, H: int, W: int, sampling: int = JPEG_420
                              ) -> Tuple[torch.Tensor, torch.Tensor]:
-    """dtk_jpeg_decode_coefficients: stream uint8 [bytes] (device), segments int64 [S, 5] (a HOST array: frame, byte offset, byte
-    length, first MCU, MCU count -- checked on the host, uploaded here), huffman uint8 [F, 3, 2, 272] (device) ->
-    (int16 [F, MCUs, 6, 64] zigzag, int32 status [F]).  Coefficients of MCUs that no segment covers are zero."""
+    """dtk_jpeg_decode_coefficients_sampled: stream uint8 [bytes] (device), segments int64 [S, 5] (a HOST array: frame, byte offset,
+    byte length, first MCU, MCU count -- checked on the host, uploaded here), huffman uint8 [F, C, 2, 272] (device; C = 3
+    components, 1 for JPEG_GRAY) -> (int16 [F, MCUs, B, 64] zigzag with B = 6 / 4 / 3 / 1 blocks per MCU, int32 status [F]).
+    Coefficients of MCUs that no segment covers are zero."""
     import numpy as np
+    B, C, _, _ = jpeg_geometry(sampling)
     seg = np.ascontiguousarray(np.asarray(segments, dtype=np.int64))
     if seg.ndim != 2 or seg.shape[1] != JPEG_SEGMENT_FIELDS or seg.shape[0] < 1:
         raise RuntimeError(f"dino_tracker_amd: segments must be int64 [S, {JPEG_SEGMENT_FIELDS}] with S >= 1, got {seg.shape}")
-    if huffman.dim() != 4 or tuple(huffman.shape[1:]) != (3, 2, JPEG_HUFF_BYTES):
-        raise RuntimeError(f"dino_tracker_amd: huffman must be uint8 [F, 3, 2, {JPEG_HUFF_BYTES}], got {tuple(huffman.shape)}")
+    if huffman.dim() != 4 or tuple(huffman.shape[1:]) != (C, 2, JPEG_HUFF_BYTES):
+        raise RuntimeError(f"dino_tracker_amd: huffman must be uint8 [F, {C}, 2, {JPEG_HUFF_BYTES}], got {tuple(huffman.shape)}")
     if stream.dim() != 1 or stream.numel() == 0:
         raise RuntimeError(f"dino_tracker_amd: stream must be uint8 [bytes], got {tuple(stream.shape)}")
     F, H, W = int(huffman.shape[0]), int(H), int(W)
-    mcus = ((H + 15) // 16) * ((W + 15) // 16)
+    mcus = jpeg_mcus(H, W, sampling)
     dev = stream.device
-    coef = torch.zeros((F, mcus, 6, 64), dtype=torch.int16, device=dev)
+    coef = torch.zeros((F, mcus, B, 64), dtype=torch.int16, device=dev)
     status = torch.empty(F, dtype=torch.int32, device=dev)
     seg_dev = torch.from_numpy(seg).to(dev)
-    check(lib().dtk_jpeg_decode_coefficients(_p(stream, torch.uint8), int(stream.numel()), _p(seg_dev), seg.ctypes.data,
-                                             int(seg.shape[0]), _p(huffman, torch.uint8), F, H, W, _p(coef), _p(status), _stream()))
+    check(lib().dtk_jpeg_decode_coefficients_sampled(int(sampling), _p(stream, torch.uint8), int(stream.numel()), _p(seg_dev),
+                                                     seg.ctypes.data, int(seg.shape[0]), _p(huffman, torch.uint8), F, H, W, _p(coef),
+                                                     _p(status), _stream()))
     return coef, status
 
 
-def jpeg_pixels(coef: torch.Tensor, qtables: torch.Tensor, H: int, W: int, status: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """dtk_jpeg_pixels: coef int16 [F, MCUs, 6, 64], qtables uint8 [F, 3, 64] (zigzag) -> uint8 [F, H, W, 3].  `status` (int32
-    [F]) receives JPEG_S_RANGE for frames with |coef * Q| > 2047."""
+def jpeg_pixels(coef: torch.Tensor, qtables: torch.Tensor, H: int, W: int, status: Optional[torch.Tensor] = None,
+                sampling: int = JPEG_420) -> torch.Tensor:
+    """dtk_jpeg_pixels_sampled: coef int16 [F, MCUs, B, 64], qtables uint8 [F, C, 64] (zigzag) -> uint8 [F, H, W, 3], for JPEG_GRAY
+    uint8 [F, H, W].  `status` (int32 [F]) receives JPEG_S_RANGE for frames with |coef * Q| > 2047."""
+    B, C, _, _ = jpeg_geometry(sampling)
     H, W = int(H), int(W)
-    mcus = ((H + 15) // 16) * ((W + 15) // 16)
-    if coef.dim() != 4 or tuple(coef.shape[1:]) != (mcus, 6, 64) or coef.shape[0] < 1:
-        raise RuntimeError(f"dino_tracker_amd: coef must be int16 [F, {mcus}, 6, 64] for {H} x {W}, got {tuple(coef.shape)}")
+    mcus = jpeg_mcus(H, W, sampling)
+    if coef.dim() != 4 or tuple(coef.shape[1:]) != (mcus, B, 64) or coef.shape[0] < 1:
+        raise RuntimeError(f"dino_tracker_amd: coef must be int16 [F, {mcus}, {B}, 64] for {H} x {W}, got {tuple(coef.shape)}")
     F = int(coef.shape[0])
-    if tuple(qtables.shape) != (F, 3, 64):
-        raise RuntimeError(f"dino_tracker_amd: qtables must be uint8 [{F}, 3, 64] (zigzag order), got {tuple(qtables.shape)}")
+    if tuple(qtables.shape) != (F, C, 64):
+        raise RuntimeError(f"dino_tracker_amd: qtables must be uint8 [{F}, {C}, 64] (zigzag order), got {tuple(qtables.shape)}")
     if status is not None and tuple(status.shape) != (F,):
         raise RuntimeError(f"dino_tracker_amd: status must be int32 [{F}], got {tuple(status.shape)}")
     dev = coef.device
-    ws = torch.empty(jpeg_decode_workspace_bytes(F, H, W), dtype=torch.uint8, device=dev)
-    out = torch.empty((F, H, W, 3), dtype=torch.uint8, device=dev)
-    check(lib().dtk_jpeg_pixels(_p(coef, torch.int16), _p(qtables, torch.uint8), F, H, W, _p(out), _p(status, torch.int32), _p(ws),
-                                _stream()))
+    ws = torch.empty(jpeg_decode_workspace_bytes(F, H, W, sampling), dtype=torch.uint8, device=dev)
+    out = torch.empty((F, H, W) if sampling == JPEG_GRAY else (F, H, W, 3), dtype=torch.uint8, device=dev)
+    check(lib().dtk_jpeg_pixels_sampled(int(sampling), _p(coef, torch.int16), _p(qtables, torch.uint8), F, H, W, _p(out),
+                                        _p(status, torch.int32), _p(ws), _stream()))
     return out
 
 

@@ -2,14 +2,17 @@
 colour conversion run in libdtk (csrc/jpeg_decode.hip; the arithmetic is defined in docs/JPEG_DECODE.md and is bit-equal to Pillow's
 decoder for the files an encoder makes).  The host only reads headers:
 
-    parse_jpeg(data)                          (JpegHeader, None) for a file the device decodes, else (None, the reason)
-    plan_jpeg(datas)                          the headers of several files of one size as the arrays the library takes
-    decode_jpeg(files_or_bytes, device)       uint8 [T, H, W, 3] on the device
-    decode_jpeg_coefficients(...)             the entropy stage alone: (int16 [T, MCUs, 6, 64] zigzag, int32 status [T], plan)
+    parse_jpeg_sampled(data)                  (JpegHeader, None) for a file the device decodes, else (None, the reason)
+    plan_jpeg_sampled(datas)                  the headers of several files of one size and sampling as the arrays the library takes
+    parse_jpeg(data), plan_jpeg(datas)        the same, for 4:2:0 files without an Adobe segment only
+    decode_jpeg(files_or_bytes, device)       uint8 [T, H, W, 3] on the device, [T, H, W, 1] for gray files
+    decode_jpeg_coefficients(...)             the entropy stage alone: (int16 [T, MCUs, B, 64] zigzag, int32 status [T], plan)
 
-Decoded on the device: baseline sequential (SOF0), 8 bit, components 1, 2, 3 sampled 2x2 / 1x1 / 1x1, ONE interleaved scan (Ss = 0,
-Se = 63, Ah = Al = 0), 8-bit quantisation tables, any Huffman tables, any restart interval, no Adobe APP14 segment.  Everything else
--- and every file whose header this parser cannot follow -- is reported with its reason and stays with the caller's host path."""
+Decoded on the device: baseline sequential (SOF0), 8 bit, ONE scan (Ss = 0, Se = 63, Ah = Al = 0) of either components 1, 2, 3
+interleaved and sampled 2x2 / 1x1 / 1x1 (4:2:0), 2x1 / 1x1 / 1x1 (4:2:2) or 1x1 / 1x1 / 1x1 (4:4:4), or of one component with id 1
+(gray, whatever sampling factors its SOF names); 8-bit quantisation tables, any Huffman tables, any restart interval; an Adobe APP14
+segment only on three components and only with transform 1 (YCbCr).  Everything else -- and every file whose header this parser
+cannot follow -- is reported with its reason and stays with the caller's host path."""
 from __future__ import annotations
 
 import io
@@ -20,23 +23,33 @@ from typing import List, Optional, Sequence, Tuple, Union
 import numpy as np
 import torch
 
+from . import ops
+
 HUFF_BYTES = 272          # DTK_JPEG_HUFF_BYTES: 16 counts + up to 256 symbols
 SEGMENT_MAX_BYTES = 1 << 28
+S420, S422, S444, GRAY = ops.JPEG_420, ops.JPEG_422, ops.JPEG_444, ops.JPEG_GRAY
+SAMPLING_NAMES = ops.JPEG_SAMPLING_NAMES
+mcus_of = ops.jpeg_mcus          # (height, width, sampling) -> MCUs of a frame
+_FACTORS = {(0x22, 0x11, 0x11): S420, (0x21, 0x11, 0x11): S422, (0x11, 0x11, 0x11): S444}
+_FACTOR_NAMES = {(0x22, 0x11, 0x11): "4:2:0", (0x21, 0x11, 0x11): "4:2:2", (0x11, 0x11, 0x11): "4:4:4", (0x12, 0x11, 0x11): "4:4:0",
+                 (0x41, 0x11, 0x11): "4:1:1"}
 
 
 @dataclass
 class JpegHeader:
     height: int
     width: int
-    qtables: np.ndarray          # uint8 [3, 64]: per component, zigzag order (as DQT stores them)
-    huffman: np.ndarray          # uint8 [3, 2, 272]: per component the DC and the AC table, counts then symbols
+    qtables: np.ndarray          # uint8 [C, 64]: per component (C = 3, gray: 1), zigzag order (as DQT stores them)
+    huffman: np.ndarray          # uint8 [C, 2, 272]: per component the DC and the AC table, counts then symbols
     restart: int                 # MCUs per restart interval, 0: none
     scan: Tuple[int, int]        # byte range of the entropy-coded data (RSTn markers included, EOI excluded)
     segments: np.ndarray         # int64 [S, 4]: byte offset in the file, byte length, first MCU, MCU count
+    sampling: int = S420         # S420, S422, S444 or GRAY
+    adobe: bool = False          # an Adobe APP14 segment with transform 1 stands in the file
 
     @property
     def mcus(self) -> int:
-        return ((self.height + 15) // 16) * ((self.width + 15) // 16)
+        return mcus_of(self.height, self.width, self.sampling)
 
 
 _SOF_OTHERS = {0xC1: "extended sequential (SOF1)", 0xC2: "progressive (SOF2)", 0xC3: "lossless (SOF3)", 0xC5: "differential (SOF5)",
@@ -62,12 +75,22 @@ def _check_huffman(cls: int, counts: Sequence[int], vals: bytes) -> Optional[str
 
 
 def parse_jpeg(data) -> Tuple[Optional[JpegHeader], Optional[str]]:
-    """Walk SOI .. SOS of one file (bytes, memoryview or uint8 array).  (header, None) when the device decodes it, else (None, why)."""
+    """Walk SOI .. SOS of one file (bytes, memoryview or uint8 array).  (header, None) for a 4:2:0 file without an Adobe segment
+    that the device decodes, else (None, why)."""
+    return _parse(data, wide=False)
+
+
+def parse_jpeg_sampled(data) -> Tuple[Optional[JpegHeader], Optional[str]]:
+    """parse_jpeg for every layout the device decodes (module docstring): the header names its `sampling`."""
+    return _parse(data, wide=True)
+
+
+def _parse(data, wide: bool) -> Tuple[Optional[JpegHeader], Optional[str]]:
     buf = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data
     n = int(buf.shape[0])
     if n < 4 or buf[0] != 0xFF or buf[1] != 0xD8:
         return None, "no SOI marker"
-    dqt, dht, restart, sof, adobe = {}, {}, 0, None, False
+    dqt, dht, restart, sof, adobe = {}, {}, 0, None, None
     i = 2
     while True:
         if i + 4 > n or buf[i] != 0xFF:
@@ -112,40 +135,48 @@ def parse_jpeg(data) -> Tuple[Optional[JpegHeader], Optional[str]]:
             restart = (seg[0] << 8) | seg[1]
         elif marker == 0xEE:
             if seg[:5] == b"Adobe":
-                adobe = True
+                adobe = seg[11] if len(seg) >= 12 else -1
         elif marker == 0xC0:
             if sof is not None:
                 return None, "two SOF0 segments"
             sof = seg
         elif marker == 0xDA:
             break
-    if adobe:
+    if adobe is not None and not wide:
         return None, "Adobe APP14 segment"
     if sof is None or len(sof) < 6:
         return None, "no SOF0 segment before the scan"
     if sof[0] != 8:
         return None, f"{sof[0]}-bit samples"
     height, width, ncomp = (sof[1] << 8) | sof[2], (sof[3] << 8) | sof[4], sof[5]
-    if ncomp != 3 or len(sof) != 6 + 3 * ncomp:
+    if ncomp not in ((1, 3) if wide else (3,)) or len(sof) != 6 + 3 * ncomp:
         return None, "grayscale (1 component)" if ncomp == 1 else f"{ncomp} components"
+    if adobe is not None and (ncomp != 3 or adobe != 1):
+        return None, (f"Adobe APP14 segment on {ncomp} component" if ncomp != 3 else
+                      f"Adobe APP14 segment with transform {adobe}, not 1 (YCbCr)" if adobe >= 0 else "Adobe APP14 segment is short")
     if height < 1 or width < 1:
         return None, "zero height or width (DNL)"
-    comps = [(sof[6 + 3 * c], sof[7 + 3 * c], sof[8 + 3 * c]) for c in range(3)]
-    if [c[0] for c in comps] != [1, 2, 3]:
-        return None, f"component ids {[c[0] for c in comps]}, not 1 2 3"
-    if [c[1] for c in comps] != [0x22, 0x11, 0x11]:
-        names = {(0x11, 0x11, 0x11): "4:4:4", (0x21, 0x11, 0x11): "4:2:2"}
-        return None, f"sampling {names.get(tuple(c[1] for c in comps), [hex(c[1]) for c in comps])}, not 4:2:0"
+    comps = [(sof[6 + 3 * c], sof[7 + 3 * c], sof[8 + 3 * c]) for c in range(ncomp)]
+    if [c[0] for c in comps] != [1, 2, 3][:ncomp]:
+        return None, f"component ids {[c[0] for c in comps]}, not {'1 2 3' if ncomp == 3 else '1'}"
+    factors = tuple(c[1] for c in comps)
+    if ncomp == 1:
+        sampling = GRAY          # a single-component scan is not interleaved: its factors change nothing
+    elif factors in _FACTORS and (wide or factors == (0x22, 0x11, 0x11)):
+        sampling = _FACTORS[factors]
+    else:
+        return None, (f"sampling {_FACTOR_NAMES.get(factors, [hex(v) for v in factors])}, not " +
+                      ("4:2:0, 4:2:2 or 4:4:4" if wide else "4:2:0"))
     if any(c[2] not in dqt for c in comps):
         return None, "a component's quantisation table is not defined"
-    if len(seg) != 10 or seg[0] != 3:
+    if len(seg) != 4 + 2 * ncomp or seg[0] != ncomp:
         return None, "several scans (the first does not hold all three components)"
-    if [seg[1], seg[3], seg[5]] != [1, 2, 3]:
+    if [seg[1 + 2 * c] for c in range(ncomp)] != [1, 2, 3][:ncomp]:
         return None, "scan components out of order"
-    if (seg[7], seg[8], seg[9]) != (0, 63, 0):
+    if tuple(seg[1 + 2 * ncomp:4 + 2 * ncomp]) != (0, 63, 0):
         return None, "the scan is not Ss = 0, Se = 63, Ah = Al = 0"
-    huff = np.zeros((3, 2, HUFF_BYTES), dtype=np.uint8)
-    for c in range(3):
+    huff = np.zeros((ncomp, 2, HUFF_BYTES), dtype=np.uint8)
+    for c in range(ncomp):
         for cls, ident in ((0, seg[2 + 2 * c] >> 4), (1, 0x10 | (seg[2 + 2 * c] & 15))):
             if ident not in dht:
                 return None, "a component's Huffman table is not defined"
@@ -163,7 +194,7 @@ def parse_jpeg(data) -> Tuple[Optional[JpegHeader], Optional[str]]:
         end, at, kinds = i + int(at[first]), at[:first], kinds[:first]
     if ((kinds < 0xD0) | (kinds > 0xD7)).any():
         return None, "a marker other than RSTn inside the scan (several scans, fill bytes or damage)"
-    mcus = ((height + 15) // 16) * ((width + 15) // 16)
+    mcus = mcus_of(height, width, sampling)
     expected = -(-mcus // restart) - 1 if restart else 0
     if at.size != expected:
         return None, f"{at.size} restart markers, {expected} expected"
@@ -176,32 +207,46 @@ def parse_jpeg(data) -> Tuple[Optional[JpegHeader], Optional[str]]:
     segments = np.stack([starts, ends - starts, first, np.minimum(per, mcus - first)], axis=1)
     if int((ends - starts).max()) > SEGMENT_MAX_BYTES:
         return None, "a segment longer than 256 MiB"
-    return JpegHeader(height, width, np.stack([dqt[c[2]] for c in comps]), huff, restart, (i, end), segments), None
+    return JpegHeader(height, width, np.stack([dqt[c[2]] for c in comps]), huff, restart, (i, end), segments, sampling,
+                      adobe is not None), None
 
 
 @dataclass
 class JpegPlan:
-    """what dtk_jpeg_decode_coefficients / dtk_jpeg_pixels take for F files of one size whose bytes lie one after the other"""
+    """what dtk_jpeg_decode_coefficients_sampled / dtk_jpeg_pixels_sampled take for F files of one size and one sampling whose bytes
+    lie one after the other"""
     frames: int
     height: int
     width: int
     segments: np.ndarray   # int64 [S, 5]: frame, byte offset in the stream, byte length, first MCU, MCU count
-    huffman: np.ndarray    # uint8 [F, 3, 2, 272]
-    qtables: np.ndarray    # uint8 [F, 3, 64]
+    huffman: np.ndarray    # uint8 [F, C, 2, 272] (C = 3 components, gray: 1)
+    qtables: np.ndarray    # uint8 [F, C, 64]
+    sampling: int = S420   # S420, S422, S444 or GRAY
 
 
 def plan_jpeg(datas: Sequence, offsets: Optional[Sequence[int]] = None) -> Tuple[Optional[JpegPlan], Optional[str]]:
-    """Parse every file; (plan, None) when all are eligible and of one size, else (None, "<index>: <reason>").  offsets[f]: where
-    file f starts in the stream the caller uploads (default: the files one after the other)."""
+    """Parse every file with parse_jpeg; (plan, None) when all are eligible and of one size, else (None, "<index>: <reason>").
+    offsets[f]: where file f starts in the stream the caller uploads (default: the files one after the other)."""
+    return _plan(datas, offsets, parse_jpeg)
+
+
+def plan_jpeg_sampled(datas: Sequence, offsets: Optional[Sequence[int]] = None) -> Tuple[Optional[JpegPlan], Optional[str]]:
+    """plan_jpeg with parse_jpeg_sampled: all files must also be of ONE sampling, the plan's."""
+    return _plan(datas, offsets, parse_jpeg_sampled)
+
+
+def _plan(datas: Sequence, offsets: Optional[Sequence[int]], parse) -> Tuple[Optional[JpegPlan], Optional[str]]:
     if not len(datas):
         return None, "no files"
     headers: List[JpegHeader] = []
     for f, data in enumerate(datas):
-        h, why = parse_jpeg(data)
+        h, why = parse(data)
         if h is None:
             return None, f"file {f}: {why}"
         if headers and (h.height, h.width) != (headers[0].height, headers[0].width):
             return None, f"file {f}: {h.height} x {h.width}, file 0 is {headers[0].height} x {headers[0].width}"
+        if headers and h.sampling != headers[0].sampling:
+            return None, f"file {f}: sampling {SAMPLING_NAMES[h.sampling]}, file 0 is {SAMPLING_NAMES[headers[0].sampling]}"
         headers.append(h)
     if offsets is None:
         offsets = np.concatenate(([0], np.cumsum([len(d) for d in datas])))[:-1]
@@ -211,7 +256,7 @@ def plan_jpeg(datas: Sequence, offsets: Optional[Sequence[int]] = None) -> Tuple
         s[:, 0], s[:, 1], s[:, 2:] = f, h.segments[:, 0] + int(off), h.segments[:, 1:]
         segs.append(s)
     return JpegPlan(len(headers), headers[0].height, headers[0].width, np.concatenate(segs),
-                    np.stack([h.huffman for h in headers]), np.stack([h.qtables for h in headers])), None
+                    np.stack([h.huffman for h in headers]), np.stack([h.qtables for h in headers]), headers[0].sampling), None
 
 
 # ---- bytes: one pinned buffer, one upload --------------------------------------------------------------------------------------
@@ -246,22 +291,22 @@ def _device(device) -> torch.device:
 
 
 def _entropy(pinned: torch.Tensor, plan: JpegPlan, device: torch.device):
-    from . import ops
     stream = pinned.to(device, non_blocking=True)
     huff = torch.from_numpy(plan.huffman).to(device)
-    return ops.jpeg_decode_coefficients(stream, plan.segments, huff, plan.height, plan.width)
+    return ops.jpeg_decode_coefficients(stream, plan.segments, huff, plan.height, plan.width, plan.sampling)
 
 
 def _planned(sources: Sequence[Source]) -> Tuple[torch.Tensor, List[np.ndarray], JpegPlan]:
     pinned, views = read_pinned(sources)
-    plan, why = plan_jpeg(views)
+    plan, why = plan_jpeg_sampled(views)
     if plan is None:
         raise ValueError(f"decode_jpeg: not decodable on the device -- {why}")
     return pinned, views, plan
 
 
 def decode_jpeg_coefficients(sources: Sequence[Source], device="cuda:0") -> Tuple[torch.Tensor, torch.Tensor, JpegPlan]:
-    """The entropy stage alone: (int16 [T, MCUs, 6, 64] in zigzag order, int32 status [T] -- ops.JPEG_S_* bits --, the plan)."""
+    """The entropy stage alone: (int16 [T, MCUs, B, 64] in zigzag order -- B = 6, 4, 3, 1 blocks per MCU for 4:2:0, 4:2:2, 4:4:4, gray --,
+    int32 status [T] -- ops.JPEG_S_* bits --, the plan)."""
     device = _device(device)
     pinned, _, plan = _planned(sources)
     coef, status = _entropy(pinned, plan, device)
@@ -270,23 +315,26 @@ def decode_jpeg_coefficients(sources: Sequence[Source], device="cuda:0") -> Tupl
 
 def decode_planned(pinned: torch.Tensor, views: List[np.ndarray], plan: JpegPlan, device, fallback: bool = True,
                    with_status: bool = False):
-    from . import ops
     device = _device(device)
     coef, status = _entropy(pinned, plan, device)
     qt = torch.from_numpy(plan.qtables).to(device)
-    out = ops.jpeg_pixels(coef, qt, plan.height, plan.width, status)
+    out = ops.jpeg_pixels(coef, qt, plan.height, plan.width, status, plan.sampling)
+    mode = "L" if plan.sampling == GRAY else "RGB"
+    if plan.sampling == GRAY:
+        out = out[..., None]
     host_status = status.cpu()                       # the one host read
     if fallback and bool(host_status.any()):
         from PIL import Image
         for f in torch.nonzero(host_status).flatten().tolist():
             with Image.open(io.BytesIO(views[f].tobytes())) as img:
-                frame = np.asarray(img.convert("RGB") if img.mode != "RGB" else img)
-            out[f] = torch.from_numpy(np.ascontiguousarray(frame)).to(device)
+                frame = np.asarray(img.convert(mode) if img.mode != mode else img)
+            out[f] = torch.from_numpy(np.ascontiguousarray(frame).reshape(tuple(out.shape[1:]))).to(device)
     return (out, host_status) if with_status else out
 
 
 def decode_jpeg(sources: Sequence[Source], device="cuda:0", fallback: bool = True, with_status: bool = False):
-    """uint8 [T, H, W, 3] on `device` from JPEG files (paths) or byte strings of one size.  ValueError with the reason when a file
+    """uint8 [T, H, W, 3] -- gray files: [T, H, W, 1] -- on `device` from JPEG files (paths) or byte strings of one size and one
+    sampling.  ValueError with the reason when a file
     is not of the kind the device decodes (module docstring).  After the launches ONE host read, the frames' status; a frame
     whose status is not zero -- a damaged stream -- is decoded by Pillow instead and uploaded into its slot (`fallback`), which
     raises what Pillow raises.  with_status: also the int32 [T] status as the device reported it (host tensor)."""

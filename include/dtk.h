@@ -951,9 +951,10 @@ int dtk_jpeg_encode(const uint8_t* frames, int32_t F, int32_t H, int32_t W, cons
                     int32_t header_bytes, uint8_t* out, size_t out_capacity, int64_t* offsets, int64_t* needed, void* workspace,
                     void* stream);
 
-/* ---- Video ingest: baseline JPEG DECODING (SOF0, 8 bit, components 1 2 3 sampled 2 x 2, 1 x 1, 1 x 1, one interleaved scan, 8-bit
- * quantisation tables, the file's own Huffman tables, any restart interval).  The arithmetic is DEFINED in docs/JPEG_DECODE.md --
- * libjpeg-turbo's default path: slow-integer IDCT, h2v2 "fancy" upsampling -- and is integer throughout.  The header is the CALLER's
+/* ---- Video ingest: baseline JPEG DECODING (SOF0, 8 bit, components 1 2 3 in one interleaved scan -- sampled 4:2:0, 4:2:2 or 4:4:4,
+ * the DTK_JPEG_* samplings below -- or one gray component, 8-bit quantisation tables, the file's own Huffman tables, any restart
+ * interval).  The arithmetic is DEFINED in docs/JPEG_DECODE.md -- libjpeg-turbo's default path: slow-integer IDCT, "fancy" h2v2 / h2v1
+ * upsampling, replication where the chroma plane is at most two samples wide -- and is integer throughout.  The header is the CALLER's
  * to parse and validate (dino_tracker_amd/video_in.py); the library sees tables and a table of segments. --------------------------
  * dtk_jpeg_decode_coefficients: the entropy stage.  stream [stream_bytes]: the files' bytes (device).  A SEGMENT is a run of
  *   entropy-coded bytes that starts byte-aligned with the DC predictors at 0 -- a restart interval without its RSTn marker, or a
@@ -974,7 +975,23 @@ int dtk_jpeg_encode(const uint8_t* frames, int32_t F, int32_t H, int32_t W, cons
  *   dtk_jpeg_decode_workspace_bytes(F, H, W) bytes, 256-byte aligned: the Y, Cb, Cr planes padded to whole MCUs (384 bytes per MCU).
  * No host synchronisation inside.  Refused with DTK_E_INVALID before anything is launched: F < 1, H or W < 1 or > 65535, null
  *   pointers, stream_bytes < 1, n_segments < 1, a segments_host entry outside the frames, the stream or the MCUs;
- *   dtk_jpeg_decode_workspace_bytes returns 0 for such sizes. */
+ *   dtk_jpeg_decode_workspace_bytes returns 0 for such sizes.
+ * The three entry points above are the 4:2:0 case of the *_sampled ones, which take the sampling first and differ only in what follows
+ *   from it.  With B blocks per MCU (in scan order) and an MCU of MW x MH pixels:
+ *     DTK_JPEG_420   components 2x2 1x1 1x1   B = 6: Y00 Y01 Y10 Y11 Cb Cr   16 x 16
+ *     DTK_JPEG_422   components 2x1 1x1 1x1   B = 4: Y0 Y1 Cb Cr             16 wide x 8 high
+ *     DTK_JPEG_444   components 1x1 1x1 1x1   B = 3: Y Cb Cr                 8 x 8
+ *     DTK_JPEG_GRAY  one component            B = 1: Y                       8 x 8  (a single-component scan is not interleaved:
+ *                                                                            one block per MCU whatever factors its SOF names)
+ *   a frame has mh mw = ceil(H / MH) ceil(W / MW) MCUs; a segment's first MCU and MCU count (and a restart interval) count those.
+ *   huffman: uint8 [F][C][2][DTK_JPEG_HUFF_BYTES] and qtables: uint8 [F][C][64] with C = 3 components, 1 for DTK_JPEG_GRAY.
+ *   coef: int16 [F][mh mw][B][64].  out: uint8 [F][H][W][3], for DTK_JPEG_GRAY uint8 [F][H][W].  workspace:
+ *   dtk_jpeg_decode_workspace_bytes_sampled(sampling, F, H, W) bytes: the planes padded to whole MCUs, 64 B bytes per MCU.
+ *   Refused with DTK_E_INVALID as above, and for a sampling that is none of the four (workspace bytes: 0). */
+#define DTK_JPEG_420 0
+#define DTK_JPEG_422 1
+#define DTK_JPEG_444 2
+#define DTK_JPEG_GRAY 3
 #define DTK_JPEG_SEGMENT_FIELDS 5
 #define DTK_JPEG_HUFF_BYTES 272
 #define DTK_JPEG_S_CODE 1     /* no Huffman code matches the next bits */
@@ -989,6 +1006,12 @@ int dtk_jpeg_decode_coefficients(const uint8_t* stream, int64_t stream_bytes, co
                                  int32_t* status, void* stream_handle);
 int dtk_jpeg_pixels(const int16_t* coef, const uint8_t* qtables, int32_t F, int32_t H, int32_t W, uint8_t* out, int32_t* status,
                     void* workspace, void* stream);
+size_t dtk_jpeg_decode_workspace_bytes_sampled(int32_t sampling, int32_t F, int32_t H, int32_t W);
+int dtk_jpeg_decode_coefficients_sampled(int32_t sampling, const uint8_t* stream, int64_t stream_bytes, const int64_t* segments,
+                                         const int64_t* segments_host, int32_t n_segments, const uint8_t* huffman, int32_t F, int32_t H,
+                                         int32_t W, int16_t* coef_out, int32_t* status, void* stream_handle);
+int dtk_jpeg_pixels_sampled(int32_t sampling, const int16_t* coef, const uint8_t* qtables, int32_t F, int32_t H, int32_t W, uint8_t* out,
+                            int32_t* status, void* workspace, void* stream);
 
 /* ---- Video and mask ingest: PNG DECODING (docs/PNG_DECODE.md): zlib / DEFLATE streams, their Adler-32, the PNG row filters.  The
  * file is the CALLER's to parse (dino_tracker_amd/png_in.py: signature, IHDR, PLTE, the IDAT payloads joined into one stream per
