@@ -134,6 +134,8 @@ SIGNATURES = {
     "dtk_vit_attention_split": (c_int, [c_void_p] * 8 + [c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "dtk_vit_gemm": (c_int, [ctypes.POINTER(VitGemmArgs), c_void_p]),
     "dtk_vit_gemm_split": (c_int, [ctypes.POINTER(VitGemmArgs), c_void_p]),
+    "dtk_vit_gemm_ws_plan": (c_int, [c_int, c_int, c_int, ctypes.c_int64, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int),
+                                     ctypes.POINTER(c_int)]),
     "dtk_delta_dino_packed_floats": (c_size_t, [c_int, c_int]),
     "dtk_delta_dino_pack": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float,
                                     c_void_p, c_void_p]),

@@ -135,6 +135,7 @@ inline GemmPath gemm_path(const dtk_vit_model* m) { return gemm_path(m->D, m->fl
 //
 //   EPI_F32 (the qkv facet)             gemm_tiled_kernel<T, EPI_F32>, always
 //   path.ws, N = K = 384, e.ln_out set  gemm_ws_ln_kernel<T>             (proj + LayerNorm-2)           gemm_ws_ln_grid     x 256
+//   gemm_ws96_runs (fc1, qkv; not ws_v1)             gemm_ws_kernel<T, EPI, 3, true, 3>                  gemm_ws96_plan(N)   x 256
 //   path.ws, K = 384 (qkv, proj, fc1)   gemm_ws_kernel<T, EPI>            (ws_v1: <T, EPI, 0>)           gemm_ws_grid(N)     x 256
 //                                       (not the qkv of SEVERAL frames shorter than its 32-row tile, S < 32: those fall through to the last line)
 //   path.ws, K != 384 (fc2: N = 384)    gemm_wide_delta_kernel<T>         (wide_v1: <T, false>;          rows / 256          x 512
@@ -145,18 +146,31 @@ inline GemmPath gemm_path(const dtk_vit_model* m) { return gemm_path(m->D, m->fl
 //
 // (path.ws and path.wide exclude each other: 384 is not a multiple of 256.  The caller sets e.ln_* only under path.fc2_ln (fc2) /
 //  path.proj_ln (proj).)
+// (gemm_ws_kernel's QKV epilogue steps (frame, position) a tile at a time and lets a tile cross ONE frame end: S >= WS_ROWS.
+//  SEVERAL shorter frames -- under 49 x 49 pixels -- put Q / K rows into the padding of the wrong frame; the tiled kernel divides per row.)
+inline bool gemm_ws_fits(int epi, long long rows, int S) { return epi != EPI_QKV || S >= WS_ROWS || rows <= S; }
+// Does this GEMM run the 96-features-per-wave form (RT = 3) of gemm_ws_kernel?  The one predicate of launch_gemm and of
+// dtk_vit_gemm_ws_plan: fc1 and qkv of the weight-stationary width, N a multiple of 384, no A / B switch.
+inline bool gemm_ws96_runs(const GemmPath& path, int epi, long long rows, int N, int K, int S, int no_store) {
+    return gemm_ws96_role(epi) && path.ws && K == WS_K && gemm_ws_fits(epi, rows, S) && !path.ws_v1 && gemm_ws96_fits(N) && !DTK_DBG(no_store, 128);
+}
+
 template <typename T, int EPI>
 int launch_gemm(const char* name, const GemmPath& path, const T* A, const T* W, long long rows, int N, int K, const GemmEpi<T>& e,
                 hipStream_t st) {
     if constexpr (EPI != EPI_F32) {
-        // (gemm_ws_kernel's QKV epilogue steps (frame, position) a tile at a time and lets a tile cross ONE frame end: S >= WS_ROWS.
-        //  SEVERAL shorter frames -- under 49 x 49 pixels -- put Q / K rows into the padding of the wrong frame; the tiled kernel divides
-        //  per row.)
-        const bool ws_fits = EPI != EPI_QKV || e.S >= WS_ROWS || rows <= e.S;
+        const bool ws_fits = gemm_ws_fits(EPI, rows, e.S);
         if constexpr (EPI == EPI_DELTA) {
             if (path.ws && K == WS_K && N == WS_K && e.ln_out) {
                 const auto gr = gemm_ws_ln_grid(rows);
                 DTK_LAUNCH(name, (gemm_ws_ln_kernel<T>), gr.first, dim3(256), 0, st, A, W, rows, e, gr.second);
+                return DTK_OK;
+            }
+        }
+        if constexpr (gemm_ws96_role(EPI)) {   // 96 features per wave, chunks by plan; every A / B switch keeps the 64-feature form
+            if (gemm_ws96_runs(path, EPI, rows, N, K, e.S, e.no_store)) {
+                const Ws96Plan plan = gemm_ws96_plan(N, rows);
+                DTK_LAUNCH(name, (gemm_ws_kernel<T, EPI, 3, true, 3>), gemm_ws96_grid(plan), dim3(256), 0, st, A, W, rows, N, e, plan);
                 return DTK_OK;
             }
         }
@@ -591,6 +605,21 @@ extern "C" int dtk_vit_gemm(const dtk_vit_gemm_args* g, void* stream) {
     return with_operand_type(g->operand_type == DTK_OPERAND_BF16, [&](auto t) {
         return run_gemm<decltype(t)>(*g, gemm_path(g->D, g->flags), vit_gemm_hidden(g), dtk_stream(stream));
     });
+}
+
+// The plan of a role that launch_gemm sends to the RT = 3 form of gemm_ws_kernel (the tests mirror it): the conditions are launch_gemm's.
+extern "C" int dtk_vit_gemm_ws_plan(int role, int D, int flags, int64_t rows, int S, int32_t* chunks, int32_t* tpc, int32_t* last) {
+    if (!chunks || !tpc || !last || rows <= 0 || (role != DTK_VIT_GEMM_FC1 && role != DTK_VIT_GEMM_QKV)) return 0;
+    const int epi = role == DTK_VIT_GEMM_FC1 ? EPI_GELU : EPI_QKV, N = role == DTK_VIT_GEMM_FC1 ? 4 * D : 3 * D;
+    if (!gemm_ws96_runs(gemm_path(D, flags), epi, rows, N, D, S, 0)) return 0;
+    const Ws96Plan p = gemm_ws96_plan(N, rows);
+    const long long tiles = dtk_cdiv(rows, WS_ROWS);
+    for (int g = 0; g < p.groups; ++g) {
+        chunks[g] = p.chunks[g];
+        tpc[g] = p.tpc[g];
+        last[g] = (int32_t)(tiles - (long long)(p.chunks[g] - 1) * p.tpc[g]);
+    }
+    return p.groups;
 }
 
 // The same stage on split operands (vit_split.h): hi / lo planes of A, of w_scale * W and of the 16-bit outputs; the residual roles

@@ -40,6 +40,74 @@ __device__ __forceinline__ void ws_for_each(F&& f, std::integer_sequence<int, I.
 template <int N, class F>
 __device__ __forceinline__ void ws_for_each(F&& f) { ws_for_each(f, std::make_integer_sequence<int, N>{}); }
 
+// ---------------------------------------------------------------------------------------------------------------
+// RT = 3 launches: column groups of 384 features on a 1-D grid laid out by a plan.  Group g owns chunks[g] consecutive workgroups,
+// each with tpc[g] consecutive token tiles (the last one of a group may be shorter): groups whose epilogue is slower can be given
+// more, smaller chunks, so that all workgroups of the one resident round end together.  All groups of fc1 are alike: four times 64;
+// qkv gives its V^T group WS96_VT_SHARE chunks and Q and K half of the rest each.
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int WS96_COLS = 384, WS96_MAX_GROUPS = 4, WS96_WGS = 256;
+constexpr int WS96_PITCH = WS96_COLS * 2 + 16;   // staged row of the Q / K tile: 768 B of payload + 16 (gemm_ws_ln_kernel's pitch)
+constexpr int WS96_STAGE_BYTES = WS_ROWS * WS96_PITCH;
+constexpr int WS96_VT_SHARE = 92;   // chunks of the V^T group of qkv (N = 1152), Q and K get 82 each; 86 would be equal shares
+constexpr int WS96_MAX_TPC = 65536;   // token tiles per chunk: 32-bit byte offsets inside a chunk (65536 x 24 KB)
+struct Ws96Plan {
+    int groups;
+    int chunks[WS96_MAX_GROUPS];   // workgroups of group g
+    int tpc[WS96_MAX_GROUPS];      // token tiles per chunk of group g
+};
+// Every tile of every group exactly once; sum of chunks <= 256 (up to 64 x 65536 tiles: beyond that the chunk size stays at its
+// 32-bit limit and the grid grows).  Fewer tiles than chunks: one tile per chunk, fewer workgroups.
+inline Ws96Plan gemm_ws96_plan(int N, long long rows) {
+    Ws96Plan p = {};
+    p.groups = N / WS96_COLS;
+    const long long tiles = (rows + WS_ROWS - 1) / WS_ROWS;
+    // qkv (three groups: Q, K, V^T): the V^T group stores 2-byte values and runs longer per tile, so it gets b > a chunks of fewer tiles:
+    // (a, a, b) with 2 a + b <= 256.  b is WS96_VT_SHARE, chosen by the sweep of docs/MEASUREMENTS.md; it depends on N, not on the input.
+    int vt_share = WS96_VT_SHARE;
+#ifdef DTK_WS96_SWEEP   // (that sweep's build: the share from the environment)
+    if (const char* sv = getenv("DTK_WS96_VT_SHARE")) vt_share = atoi(sv);
+#endif
+    for (int g = 0; g < p.groups; ++g) {
+        const int share = p.groups != 3 ? WS96_WGS / p.groups : g == 2 ? vt_share : (WS96_WGS - vt_share) / 2;
+        long long tpc = (tiles + share - 1) / share;
+        if (tpc < 1) tpc = 1;
+        if (tpc > WS96_MAX_TPC) tpc = WS96_MAX_TPC;
+        p.tpc[g] = (int)tpc;
+        p.chunks[g] = (int)((tiles + tpc - 1) / tpc);
+    }
+    return p;
+}
+constexpr bool gemm_ws96_role(int epi) { return epi == EPI_GELU || epi == EPI_QKV; }   // the epilogues that have this form
+inline bool gemm_ws96_fits(int N) { return N % WS96_COLS == 0 && N / WS96_COLS >= 1 && N / WS96_COLS <= WS96_MAX_GROUPS; }
+inline dim3 gemm_ws96_grid(const Ws96Plan& p) {
+    unsigned n = 0;
+    for (int g = 0; g < p.groups; ++g) n += (unsigned)p.chunks[g];
+    return dim3(n);
+}
+// What a workgroup owns.  RT = 2: the launch's last argument is the tiles per chunk, blockIdx.x the column group, blockIdx.y the chunk.
+// RT = 3: the argument is the plan, blockIdx.x counts the chunks of group 0, then those of group 1, ...
+struct WsWhere {
+    unsigned colgroup;
+    int tpc;
+    unsigned chunk;   // the workgroup's first token tile is chunk * tpc
+};
+template <int RT> struct WsArg { typedef int type; };
+template <> struct WsArg<3> { typedef Ws96Plan type; };
+__device__ __forceinline__ WsWhere ws_where(int tiles_per_chunk) {
+    return {blockIdx.x, tiles_per_chunk, blockIdx.y};
+}
+__device__ __forceinline__ WsWhere ws_where(const Ws96Plan& plan) {
+    // (constant indices into the plan: a variable one would move the kernel argument into scratch memory)
+    int c = blockIdx.x, g = 0, tpc = plan.tpc[0], first = 0;
+#pragma unroll
+    for (int i = 0; i + 1 < WS96_MAX_GROUPS; ++i) {
+        first += plan.chunks[i];
+        if (i + 1 < plan.groups && (int)blockIdx.x >= first) { g = i + 1; c = (int)blockIdx.x - first; tpc = plan.tpc[i + 1]; }
+    }
+    return {(unsigned)g, tpc, (unsigned)c};
+}
+
 // V2M (round 4, default 3): bit 0 = weights in AGPRs (loaded there by asm; the builtin MFMA takes them from there as they are)
 // and zero accumulators through the MFMA's C operand; bit 1 = token tiles by LDS-DMA through a buffer descriptor (scalar tile
 // offset + constant per-lane offset: 3 issue slots per request instead of ~13).  V2M = 0 is the round 1-3 form, kept for the
@@ -47,38 +115,55 @@ __device__ __forceinline__ void ws_for_each(F&& f) { ws_for_each(f, std::make_in
 // HC (default with V2M = 3): the hand-cut step described above; <T, EPI, 3, false> is the form before it (DTK_DEV bit 128, and any
 // N that is not a multiple of 64).  V2M = 0 shares none of the hand-cut code: it is the bitwise reference of
 // tests/test_gpu_vit_gemm_ws_epilogue.py.
-template <typename T, int EPI, int V2M = 3, bool HC = (V2M == 3)>
+//
+// RT: 32-row weight tiles per wave.  RT = 2 is the form described so far.  RT = 3 (hand-cut form only, fc1 and qkv) gives a wave 96
+// features and a workgroup 384: the same token tile, fetch, barrier and fragment reads serve 72 MFMAs instead of 48 -- one
+// ds_read_b128 feeds three -- and every output is still the same chain of 24 MFMAs, so the bits do not change.  288 weight registers,
+// 240 of them AGPRs (as in gemm_ws_ln_kernel); the bias of a group of eight values comes from the s_bias table in the group's first
+// slot instead of living in registers.  qkv at RT = 3: column group g is q, k or v, so a workgroup is all-Q, all-K or all-V^T; Q / K
+// stage the workgroup's [32][384] tile in LDS (double-buffered) and flush it as whole 128-byte (token, head) lines behind the barrier
+// that completes it, six ds_read_b128 behind the first MFMA of the next step and six stores behind the following ones; V^T stores one
+// 2-byte value per slot in slots 0 .. 47.
+template <typename T, int EPI, int V2M = 3, bool HC = (V2M == 3), int RT = 2>
 __global__ __launch_bounds__(256) void gemm_ws_kernel(const T* __restrict__ A, const T* __restrict__ Wt,
-                                                      long long M, int N, GemmEpi<T> e, int tiles_per_chunk) {
+                                                      long long M, int N, GemmEpi<T> e, typename WsArg<RT>::type where) {
     typedef typename Vec<T>::t8 T8;
     typedef typename Vec<T>::t4 T4;
     (void)sizeof(T8); (void)sizeof(T4);
     constexpr bool V2 = (V2M & 1) != 0;       // AGPR weights + zero C operand
     constexpr bool V2D = (V2M & 2) != 0;      // descriptor LDS-DMA
     static_assert(!HC || V2M == 3, "the hand-cut step is built on the AGPR weights and the descriptor LDS-DMA");
+    static_assert(RT == 2 || (RT == 3 && HC && (EPI == EPI_GELU || EPI == EPI_QKV)), "96 features per wave: the hand-cut fc1 and qkv steps only");
+    constexpr int WCOLS = 32 * RT;                  // features per wave
+    constexpr int AGPR_FRAGS = RT == 2 ? 2 * WS_KS : 60;   // weight fragments pinned to AGPRs by asm (RT = 3: 240 of the 256, of 72)
     operand_mode<T>();
     __shared__ __attribute__((aligned(1024))) unsigned char toks[3][WS_TILE_BYTES];
     __shared__ __attribute__((aligned(16))) unsigned char stage[4][2][WS_UNIT_BYTES];  // per wave: two staging units
-    __shared__ __attribute__((aligned(16))) float s_bias[4][64], s_gamma[4][64];
+    // RT = 3, Q / K: the workgroup's [32][384] 16-bit tile, padded pitch, double-buffered (a wave's 96 features are one and a half heads)
+    constexpr bool STG3 = RT == 3 && EPI == EPI_QKV;
+    __shared__ __attribute__((aligned(16))) unsigned char stage3[STG3 ? 2 : 1][STG3 ? WS96_STAGE_BYTES : 16];
+    __shared__ __attribute__((aligned(16))) float s_bias[4][WCOLS], s_gamma[4][64];
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int j = lane & 31, h = lane >> 5;
-    const int n0 = blockIdx.x * WS_COLS + w * 64;
+    const WsWhere wh = ws_where(where);
+    const int tiles_per_chunk = wh.tpc;
+    const int n0 = wh.colgroup * (4 * WCOLS) + w * WCOLS;
     const long long total_tiles = (M + WS_ROWS - 1) / WS_ROWS;
-    const long long tile0 = (long long)blockIdx.y * tiles_per_chunk;
+    const long long tile0 = (long long)wh.chunk * tiles_per_chunk;
     if (tile0 >= total_tiles) return;
     const int NT = (int)((total_tiles - tile0) < tiles_per_chunk ? (total_tiles - tile0) : tiles_per_chunk);
     // weights: MFMA row i of row tile t carries output feature n0 + 32 t + nl(i), nl chosen so that D row
     // (r & 3) + 8 (r >> 2) + 4 h  <->  feature 16 h + r
     const int nl = (j & 3) + 4 * (j >> 3) + 16 * ((j >> 2) & 1);
-    T8 wf[2][WS_KS];
+    T8 wf[RT][WS_KS];
 #pragma unroll
-    for (int t = 0; t < 2; ++t) {
+    for (int t = 0; t < RT; ++t) {
         const int row = min(n0 + t * 32 + nl, N - 1);
         const T* wp = Wt + (size_t)row * WS_K + h * 8;
 #pragma unroll
         for (int ks = 0; ks < WS_KS; ++ks) {
-            if (V2) asm volatile("global_load_dwordx4 %0, %1, off" : "=a"(wf[t][ks]) : "v"(wp + ks * 16) : "memory");
+            if (V2 && t * WS_KS + ks < AGPR_FRAGS) asm volatile("global_load_dwordx4 %0, %1, off" : "=a"(wf[t][ks]) : "v"(wp + ks * 16) : "memory");
             else wf[t][ks] = *reinterpret_cast<const T8*>(wp + ks * 16);
         }
     }
@@ -88,9 +173,10 @@ __global__ __launch_bounds__(256) void gemm_ws_kernel(const T* __restrict__ A, c
         // wf can be scheduled above its re-definition -- ADVICE r4: before, only scheduling luck kept uses behind the wait)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #pragma unroll
-        for (int t = 0; t < 2; ++t)
+        for (int t = 0; t < RT; ++t)
 #pragma unroll
-            for (int ks = 0; ks < WS_KS; ++ks) asm volatile("" : "+a"(wf[t][ks]));
+            for (int ks = 0; ks < WS_KS; ++ks)
+                if (t * WS_KS + ks < AGPR_FRAGS) asm volatile("" : "+a"(wf[t][ks]));
     }
     if constexpr (!HC) {
         const int n = min(n0 + lane, N - 1);
@@ -192,14 +278,21 @@ __global__ __launch_bounds__(256) void gemm_ws_kernel(const T* __restrict__ A, c
         // bias (and LayerScale) of this lane's 2 x 16 features: registers for the whole chunk (the launcher gives this form whole
         // 64-column waves only: N % 64 == 0)
         float bia[2][16], gam[2][16];
+        if constexpr (RT == 2) {
 #pragma unroll
-        for (int t = 0; t < 2; ++t)
+            for (int t = 0; t < 2; ++t)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int nf = n0 + 32 * t + 16 * h + r;
-                bia[t][r] = e.bias ? e.bias[nf] : 0.f;
-                gam[t][r] = (EPI == EPI_DELTA) ? e.gamma[nf] : 1.f;
-            }
+                for (int r = 0; r < 16; ++r) {
+                    const int nf = n0 + 32 * t + 16 * h + r;
+                    bia[t][r] = e.bias ? e.bias[nf] : 0.f;
+                    gam[t][r] = (EPI == EPI_DELTA) ? e.gamma[nf] : 1.f;
+                }
+        } else {
+            // RT = 3: 3 x 16 bias registers do not fit beside the GELU chains.  The wave's 96 values go into its row of s_bias (read
+            // back by this wave only, eight at a time, in the first slot of each group of eight values; `sb` in the slots is the lane's base there).
+            (void)bia; (void)gam;
+            for (int i = lane; i < WCOLS; i += 64) s_bias[w][i] = e.bias ? e.bias[n0 + i] : 0.f;
+        }
         const bool dbg_nost = DTK_DBG(e.no_store, 3) || DTK_DBG(e.no_store, 32);   // DTK_DEV: no stores (32: the arithmetic stays live)
         const bool dbg_noar = DTK_DBG(e.no_store, 64);                              // DTK_DEV: bias + convert only, stores kept
         auto run = [&](auto vt_tag) {
@@ -228,6 +321,11 @@ __global__ __launch_bounds__(256) void gemm_ws_kernel(const T* __restrict__ A, c
                     up = (which == 0 ? e.q : e.k) + (((size_t)f0 * e.heads + head) * e.Sp + s0) * 64;
                     cross = (unsigned)((e.heads * e.Sp - e.S) * 64);
                 }
+                if constexpr (RT == 3) {
+                    // the workgroup is all-Q, all-K or all-V^T.  V^T rows (head, dh) are the wave's features 96 w ..; Q / K start at head 0
+                    if (VT) up = e.vt + ((size_t)f0 * e.heads * 64 + (n0 - which * e.D)) * e.Sp + s0;
+                    else up = (which == 0 ? e.q : e.k) + ((size_t)f0 * e.heads * e.Sp + s0) * 64;
+                }
             }
             const size_t out_step = (size_t)WS_ROWS * N;
             unsigned char* const sw = &stage[w][0][0] + j * WS_PITCH + 32 * h;                         // staging: this lane's 16 features of token j
@@ -249,28 +347,92 @@ __global__ __launch_bounds__(256) void gemm_ws_kernel(const T* __restrict__ A, c
             float v[8];
             f2 sx[4], uu[4], pp[4];
             T8 o;
-            dtk_u4 fv[4];
+            constexpr int NFL = STG3 ? 6 : 4;   // flush pieces per lane and tile
+            dtk_u4 fv[NFL];
             unsigned voff = 0;
+            // RT = 3 Q / K: `sto` = byte offset of the staging buffer this step's epilogue writes (0: tiles in accA, WS96_STAGE_BYTES: accB); the
+            // flush reads the other one.  Lane (row tid / 8, piece lane % 8) flushes that row's 128-byte line of head p, p = 0 .. 5.
+            unsigned sto = 0, flo = 0;
+            unsigned char* const sw3 = STG3 ? &stage3[0][0] + j * WS96_PITCH + (w * WCOLS + 16 * h) * 2 : nullptr;
+            const unsigned char* const sr3 = STG3 ? &stage3[0][0] + (tid >> 3) * WS96_PITCH + (lane & 7) * 16 : nullptr;
             constexpr float GC[9] = {1.112979639e-10f, -1.065557687e-08f, 4.510875158e-07f, -1.125288873e-05f, 1.868377149e-04f,
                                      -2.217123518e-03f, 1.963194646e-02f, -1.326889843e-01f, 7.978046536e-01f};   // gelu2
             auto flush_reads = [&]() {
-                ws_for_each<4>([&](auto p_tag) {
+                ws_for_each<NFL>([&](auto p_tag) {
                     constexpr int p = decltype(p_tag)::value;
-                    fv[p] = *reinterpret_cast<const dtk_u4*>(sr + 8 * p * WS_PITCH);
+                    if constexpr (STG3) fv[p] = *reinterpret_cast<const dtk_u4*>(sr3 + flo + 128 * p);
+                    else fv[p] = *reinterpret_cast<const dtk_u4*>(sr + 8 * p * WS_PITCH);
                 });
             };
             auto flush_store = [&](auto pred_tag, auto p_tag, int valid) {
                 constexpr int p = decltype(p_tag)::value;
+                if constexpr (STG3) {
+                    const int row3 = tid >> 3;
+                    const bool ok3 = decltype(pred_tag)::value ? row3 < valid : true;
+                    st16(up, (unsigned)(row3 * 64 + (lane & 7) * 8 + p * e.Sp * 64) + (s0 + row3 >= e.S ? cross : 0u), fv[p], ok3);
+                    return;
+                }
                 const int row = 8 * p + (lane >> 3);
                 const bool ok = decltype(pred_tag)::value ? row < valid : true;
                 if constexpr (EPI == EPI_DELTA) st16(up, (unsigned)(row * N + (lane & 7) * 8), fv[p], ok);
                 else st16(up, (unsigned)(row * 64 + (lane & 7) * 8) + (s0 + row >= e.S ? cross : 0u), fv[p], ok);
             };
-            auto slot = [&](auto pred_tag, auto fl_tag, const f16v (&acc)[2], auto s_tag, int valid) {
+            float4 bi0, bi1, bj0, bj1;   // RT = 3: the bias of the group of eight values in flight (V^T: two sets, the next group's on its way)
+            auto slot = [&](auto pred_tag, auto fl_tag, const f16v (&acc)[RT], auto s_tag, int valid) {
                 constexpr bool PRED = decltype(pred_tag)::value, FL = decltype(fl_tag)::value;
                 constexpr int s = decltype(s_tag)::value;
                 const bool ok = PRED ? j < valid : true;
-                if constexpr (EPI == EPI_GELU) {
+                if constexpr (EPI == EPI_GELU && RT == 3) {
+                    const float* const sb = &s_bias[w][16 * h];
+                    // six groups of eight values, 12 slots each: the RT = 2 schedule one slot later, its free last slot taken by the
+                    // bias read in front (the read's latency passes under the MFMA between slots 0 and 1)
+                    constexpr int u = s / 12, ph = s % 12, t = u >> 1, hv = u & 1;
+                    if (ph == 0) {
+                        bi0 = *reinterpret_cast<const float4*>(sb + 32 * t + 8 * hv);
+                        bi1 = *reinterpret_cast<const float4*>(sb + 32 * t + 8 * hv + 4);
+                    } else if (ph <= 2) {
+                        const float4 bq = ph == 1 ? bi0 : bi1;
+                        const float bb[4] = {bq.x, bq.y, bq.z, bq.w};
+#pragma unroll
+                        for (int r = 4 * (ph - 1); r < 4 * (ph - 1) + 4; ++r) v[r] = acc[t][8 * hv + r] + bb[r & 3];
+                        if (IsF16<T>::value) {   // the stored GELU(v): the positive part of v
+#pragma unroll
+                            for (int r = 4 * (ph - 1); r < 4 * (ph - 1) + 4; r += 2) amax = fmaxf(fmaxf(amax, v[r]), v[r + 1]);
+                        }
+                    }
+                    if (dbg_noar) {
+                        if (ph == 10) {
+#pragma unroll
+                            for (int r = 0; r < 8; ++r) o[r] = (T)v[r];
+                        }
+                    } else if (ph == 3) {   // gelu2, its four chains side by side
+                        const f2 c = {4.25f, 4.25f};
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) sx[q] = __builtin_elementwise_min(__builtin_elementwise_max(f2{v[2 * q], v[2 * q + 1]}, -c), c);
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) uu[q] = sx[q] * sx[q];
+                    } else if (ph >= 4 && ph <= 7) {
+#pragma unroll
+                        for (int l = 2 * (ph - 4); l < 2 * (ph - 4) + 2; ++l)
+#pragma unroll
+                            for (int q = 0; q < 4; ++q)
+                                pp[q] = __builtin_elementwise_fma(l == 0 ? f2{GC[0], GC[0]} : pp[q], uu[q], f2{GC[l + 1], GC[l + 1]});
+                    } else if (ph == 8) {
+                        const f2 one = {1.f, 1.f};
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) pp[q] = __builtin_elementwise_min(__builtin_elementwise_max(sx[q] * pp[q], -one), one);
+                    } else if (ph == 9) {
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) {
+                            const f2 hx = f2{v[2 * q], v[2 * q + 1]} * f2{0.5f, 0.5f};
+                            uu[q] = __builtin_elementwise_fma(hx, pp[q], hx);
+                        }
+                    } else if (ph == 10) {
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) { o[2 * q] = (T)uu[q][0]; o[2 * q + 1] = (T)uu[q][1]; }
+                    }
+                    if (ph == 11) st16(op, (unsigned)(32 * t + 8 * hv), __builtin_bit_cast(dtk_u4, o), ok);
+                } else if constexpr (EPI == EPI_GELU) {
                     constexpr int u = s / 12, ph = s % 12, t = u >> 1, hv = u & 1;
                     if (ph < 2) {
 #pragma unroll
@@ -316,6 +478,56 @@ __global__ __launch_bounds__(256) void gemm_ws_kernel(const T* __restrict__ A, c
                         //  session -- the 16-byte pieces stay; docs/NEGATIVE_RESULTS.md)
                         st16(op, (unsigned)(32 * t + 8 * hv), __builtin_bit_cast(dtk_u4, o), ok);
                     }
+                } else if constexpr (STG3 && STG) {
+                    const float* const sb = &s_bias[w][16 * h];
+                    // Q / K at RT = 3: the RT = 2 schedule of a group of eight values (a pair every other slot, one ds_write_b128 in slot 9)
+                    // into the workgroup's tile; the group's bias from s_bias in slot 0; six flush pieces behind the first MFMA
+                    if constexpr (FL && s == 0) flush_reads();
+                    if constexpr (FL && s >= 1 && s <= NFL) flush_store(No{}, std::integral_constant<int, s - 1>{}, WS_ROWS);
+                    constexpr int u = s / 12, ph = s % 12, t = u >> 1, hv = u & 1;
+                    if constexpr (ph == 0) {
+                        bi0 = *reinterpret_cast<const float4*>(sb + 32 * t + 8 * hv);
+                        bi1 = *reinterpret_cast<const float4*>(sb + 32 * t + 8 * hv + 4);
+                    } else if constexpr ((ph & 1) && ph < 9) {
+                        constexpr int r0 = (ph - 1) & 7, r1 = ph & 7;   // this slot's pair of values
+                        const float bb[8] = {bi0.x, bi0.y, bi0.z, bi0.w, bi1.x, bi1.y, bi1.z, bi1.w};
+                        const float v0 = acc[t][8 * hv + r0] + bb[r0], v1 = acc[t][8 * hv + r1] + bb[r1];
+                        if (IsF16<T>::value && !dbg_noar) amax = amax2(amax, v0 * qsc, v1 * qsc);
+                        if (dbg_noar) { o[r0] = (T)v0; o[r1] = (T)v1; }
+                        else { o[r0] = (T)(v0 * qsc); o[r1] = (T)(v1 * qsc); }
+                    } else if constexpr (ph == 9) {
+                        *reinterpret_cast<T8*>(sw3 + sto + 64 * t + 16 * hv) = o;
+                    }
+                } else if constexpr (STG3) {
+                    const float* const sb = &s_bias[w][16 * h];
+                    // V^T at RT = 3: 48 values, one 2-byte store per slot in slots 0 .. 47; row (head, dh) = the wave's feature.  The bias of
+                    // group u + 1 is read in slot 3 of group u (group 0: in slot 0) into the other of two register sets
+                    if constexpr (s == 0) {
+                        voff = (unsigned)(16 * h * e.Sp + j) + (s0 + j >= e.S ? cross : 0u);
+                        bi0 = *reinterpret_cast<const float4*>(sb);
+                        bi1 = *reinterpret_cast<const float4*>(sb + 4);
+                    }
+                    if constexpr (s < 16 * RT) {
+                        constexpr int u = s / 8, r = s % 8, t = u >> 1, hv = u & 1;
+                        if constexpr (r == 3 && u + 1 < 2 * RT) {
+                            constexpr int tn = (u + 1) >> 1, hn = (u + 1) & 1;
+                            if constexpr (u & 1) {
+                                bi0 = *reinterpret_cast<const float4*>(sb + 32 * tn + 8 * hn);
+                                bi1 = *reinterpret_cast<const float4*>(sb + 32 * tn + 8 * hn + 4);
+                            } else {
+                                bj0 = *reinterpret_cast<const float4*>(sb + 32 * tn + 8 * hn);
+                                bj1 = *reinterpret_cast<const float4*>(sb + 32 * tn + 8 * hn + 4);
+                            }
+                        }
+                        const float4 q0 = (u & 1) ? bj0 : bi0, q1 = (u & 1) ? bj1 : bi1;
+                        const float bb[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
+                        v[r] = acc[t][8 * hv + r] + bb[r];
+                        if (IsF16<T>::value && (r & 1) && !dbg_noar) amax = amax2(amax, v[r - 1] * qsc, v[r] * qsc);
+                        const T val = (T)v[r];
+                        T* const p = up + (size_t)(32 * t + 8 * hv + r) * e.Sp;
+                        if (!dbg_nost) { if (ok) p[voff] = val; }
+                        else dbg_fold(typename Vec<T>::t2{val, val});
+                    }
                 } else if constexpr (STG) {
                     if constexpr (FL && s == 0) flush_reads();
                     if constexpr (FL && s >= 1 && s <= 4) flush_store(No{}, std::integral_constant<int, s - 1>{}, WS_ROWS);
@@ -345,27 +557,27 @@ __global__ __launch_bounds__(256) void gemm_ws_kernel(const T* __restrict__ A, c
                     }
                 }
             };
-            auto tail_epi = [&](const f16v (&acc)[2], int valid) {
-                ws_for_each<2 * WS_KS>([&](auto s_tag) { slot(Yes{}, No{}, acc, s_tag, valid); });
+            auto tail_epi = [&](const f16v (&acc)[RT], int valid) {
+                ws_for_each<RT * WS_KS>([&](auto s_tag) { slot(Yes{}, No{}, acc, s_tag, valid); });
                 if (!STG) next_tile();
             };
             auto tail_flush = [&](int valid) {
                 if constexpr (STG) {
                     flush_reads();
-                    ws_for_each<4>([&](auto p_tag) { flush_store(Yes{}, p_tag, valid); });
+                    ws_for_each<NFL>([&](auto p_tag) { flush_store(Yes{}, p_tag, valid); });
                     next_tile();
                 }
             };
             // one step: the MFMAs of the tile in `buf` into accN; PREV: behind each, a slot of the previous tile's epilogue (accP)
-            auto step = [&](auto prev_tag, auto fl_tag, int buf, f16v (&accN)[2], const f16v (&accP)[2]) {
+            auto step = [&](auto prev_tag, auto fl_tag, int buf, f16v (&accN)[RT], const f16v (&accP)[RT]) {
                 constexpr bool PREV = decltype(prev_tag)::value, FL = decltype(fl_tag)::value;
                 const unsigned char* base = &toks[0][0] + buf * WS_TILE_BYTES;
                 const f16v zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};   // inline constant C
                 T8 b[3];
                 b[0] = *reinterpret_cast<const T8*>(base + frag_off[0]);
                 b[1] = *reinterpret_cast<const T8*>(base + frag_off[1]);
-                ws_for_each<2 * WS_KS>([&](auto s_tag) {
-                    constexpr int ks = decltype(s_tag)::value / 2, t = decltype(s_tag)::value % 2;
+                ws_for_each<RT * WS_KS>([&](auto s_tag) {
+                    constexpr int ks = decltype(s_tag)::value / RT, t = decltype(s_tag)::value % RT;
                     if constexpr (t == 0 && ks + 2 < WS_KS)
                         b[(ks + 2) % 3] = *reinterpret_cast<const T8*>(base + frag_off[(ks + 2) & 7] + ((ks + 2) >> 3) * 1024);
                     // (the builtin, not an asm MFMA: see the V2M = 0 .. 3 step below)
@@ -379,7 +591,7 @@ __global__ __launch_bounds__(256) void gemm_ws_kernel(const T* __restrict__ A, c
                 // (staged forms: `up` follows the FLUSHED tile, two behind; the others the epilogue's tile, one behind)
                 if (STG ? FL : PREV) next_tile();
             };
-            f16v accA[2], accB[2];
+            f16v accA[RT], accB[RT];
             issue(0, 0);
             issue(min(1, NT - 1), 1);
             dtk_vm_wait<WS_LQ>();
@@ -389,11 +601,13 @@ __global__ __launch_bounds__(256) void gemm_ws_kernel(const T* __restrict__ A, c
                 constexpr bool FIRST = decltype(first_tag)::value;
                 const int b1 = b0 == 2 ? 0 : b0 + 1, b2 = b1 == 2 ? 0 : b1 + 1;
                 issue(min(n + 2, NT - 1), b2);
+                if constexpr (STG3) { sto = WS96_STAGE_BYTES; flo = 0; }   // (epilogue of a tile in accB, flush of the accA tile before it)
                 if (FIRST) step(No{}, No{}, b0, accA, accB);
                 else step(Yes{}, Yes{}, b0, accA, accB);
                 dtk_vm_wait<WS_LQ>();
                 __syncthreads();
                 issue(min(n + 3, NT - 1), b0);
+                if constexpr (STG3) { sto = 0; flo = WS96_STAGE_BYTES; }
                 if (FIRST) step(Yes{}, No{}, b1, accB, accA);
                 else step(Yes{}, Yes{}, b1, accB, accA);
                 dtk_vm_wait<WS_LQ>();
@@ -407,14 +621,31 @@ __global__ __launch_bounds__(256) void gemm_ws_kernel(const T* __restrict__ A, c
             const int valid = left < WS_ROWS ? (int)left : WS_ROWS;
             const bool odd = n < NT;  // one more tile
             if (odd) {
+                if constexpr (STG3) { sto = WS96_STAGE_BYTES; flo = 0; }
                 if (n > 0) step(Yes{}, Yes{}, b0, accA, accB);
                 else step(No{}, No{}, b0, accA, accB);
+            }
+            if constexpr (STG3 && STG) {
+                // the staging tile is the workgroup's: the tile staged in an odd last step is complete, and every wave's flush reads of the
+                // other buffer are done, only behind a barrier; the last tile then goes into the buffer its accumulators' parity names
+                __syncthreads();
+                flo = odd ? WS96_STAGE_BYTES : 0;
+                sto = odd ? 0 : WS96_STAGE_BYTES;
             }
             if (NT > 1) tail_flush(WS_ROWS);
             // (the last tile's accumulators by VALUE: two calls of the tail on accA / accB are merged into one on a pointer, which
             //  takes both arrays out of the registers for the whole kernel)
-            const f16v accL[2] = {odd ? accA[0] : accB[0], odd ? accA[1] : accB[1]};
-            tail_epi(accL, valid);
+            if constexpr (RT == 2) {
+                const f16v accL[2] = {odd ? accA[0] : accB[0], odd ? accA[1] : accB[1]};
+                tail_epi(accL, valid);
+            } else {
+                const f16v accL[3] = {odd ? accA[0] : accB[0], odd ? accA[1] : accB[1], odd ? accA[2] : accB[2]};
+                tail_epi(accL, valid);
+            }
+            if constexpr (STG3 && STG) {
+                __syncthreads();
+                flo = sto;
+            }
             tail_flush(valid);
         };
         if constexpr (EPI == EPI_QKV) {

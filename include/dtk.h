@@ -227,6 +227,12 @@ typedef struct dtk_vit_gemm_args {
 } dtk_vit_gemm_args;
 int dtk_vit_gemm(const dtk_vit_gemm_args* g, void* stream);
 int dtk_vit_gemm_split(const dtk_vit_gemm_args* g, void* stream);
+/* How dtk_vit_gemm / dtk_vit_forward lay a role's launch out when it runs the 96-features-per-wave weight-stationary kernel (D = 384,
+ * roles FC1 and QKV without TILED_GEMMS / GEMM_WS_V1; S = tokens per frame, used by QKV only: several frames shorter than 32 rows
+ * run another kernel): returns the number of 384-column groups, 0 when the role does not run that kernel under these flags.  Group g
+ * runs as chunks[g] workgroups of tpc[g] consecutive 32-row token tiles, the last of them with last[g] tiles; the arrays hold four
+ * entries.  Host arithmetic only: no device is touched. */
+int dtk_vit_gemm_ws_plan(int role, int D, int flags, int64_t rows, int S, int32_t* chunks, int32_t* tpc, int32_t* last);
 
 /* ---- P2: Delta-DINO refinement (models/tracker.py:113-135; models/networks/delta_dino.py:53-61;
  *      models/utils.py:7-45), fp32-grade on the fp16 MFMA (operands split into hi + lo halves, 3 products) ----------

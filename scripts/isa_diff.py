@@ -2,6 +2,8 @@
 """Is the gfx950 machine code of two builds the same, function by function?  (CPU only.)
 
     python scripts/isa_diff.py old/vit.o new/vit.o        # host objects with a .hip_fatbin section, or bare code objects
+    python scripts/isa_diff.py old/vit.o new/vit.o --rename REGEX REPLACEMENT   # re.sub on the OLD symbols first (a template that
+                                                                                # gained a defaulted argument changes its mangled names)
 
 Unbundles the gfx950 code object (the objcopy + clang-offload-bundler recipe of tests/test_abi.py::test_m0_users and
 scripts/kernel_resources.sh), disassembles it and compares, per function symbol, the instruction list -- addresses and
@@ -76,10 +78,13 @@ def resources(co):
     return out
 
 
-def main(old, new):
+def main(old, new, rename=None):
     with tempfile.TemporaryDirectory() as t0, tempfile.TemporaryDirectory() as t1:
         co0, co1 = code_object(old, t0), code_object(new, t1)
         f0, f1, r0, r1 = functions(co0), functions(co1), resources(co0), resources(co1)
+    if rename:   # a template that gained a defaulted argument: the old symbols under their new names
+        f0 = {re.sub(rename[0], rename[1], k): v for k, v in f0.items()}
+        r0 = {re.sub(rename[0], rename[1], k): v for k, v in r0.items()}
     bad = 0
     for name in sorted(set(f0) | set(f1)):
         if name not in f0 or name not in f1:
@@ -98,6 +103,8 @@ def main(old, new):
 
 
 if __name__ == "__main__":
+    if len(sys.argv) == 6 and sys.argv[3] == "--rename":
+        sys.exit(main(sys.argv[1], sys.argv[2], (sys.argv[4], sys.argv[5])))
     if len(sys.argv) != 3:
         sys.exit(__doc__)
     sys.exit(main(sys.argv[1], sys.argv[2]))
