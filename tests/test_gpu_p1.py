@@ -241,6 +241,7 @@ def test_attention_guards_and_safe_pass(dt, kernel):
     2^40 / 2^120); (6) scores of +-300 -> poisoned sum -> safe pass; (7) about -300 for EVERY key -> an estimate far
     below 0; (8) a row whose large scores all sit in LATE tiles: the estimate is low and the sums jump past POISON_T in one
     step (fp16); and ordinary rows that share their wave with them.  S is not a multiple of the 64-key tile (masked tail)."""
+    import vit_attention_ref as R
     from dino_tracker_amd import ops
     from dino_tracker_amd._lib import OPERAND_ATTENTION_V4, OPERAND_BF16, OPERAND_F16, check, lib
     tdt = torch.float16 if dt == "fp16" else torch.bfloat16
@@ -271,14 +272,11 @@ def test_attention_guards_and_safe_pass(dt, kernel):
     check(lib().dtk_vit_attention(ops._p(qd), ops._p(kd), ops._p(vd), ops._p(out), F, Hh, S, Sp,
                                   (OPERAND_F16 if dt == "fp16" else OPERAND_BF16) | (OPERAND_ATTENTION_V4 if kernel == "v4" else 0),
                                   ops._stream()))
-    s = qb.double()[:, :, :S] @ kb.double()[:, :, :S].transpose(2, 3)            # exp2-domain scores
-    p = torch.softmax(s * 0.6931471805599453, dim=-1)
-    ref = (p @ vb.double()[:, :, :S]).permute(0, 2, 1, 3).reshape(F, S, Hh * 64)
+    s = R.scores(qb, kb, S)                                                      # exp2-domain scores
+    ref = R.reference(qb, kb, vb, S)
     got = out.double().cpu()
     assert torch.isfinite(got).all()
-    err = (got - ref).abs().amax(dim=-1)[0]
-    scale = ref.abs().amax(dim=-1)[0].clamp(min=0.05)
-    rel = err / scale
+    rel = R.row_rel(got, ref)[0]
     # 16-bit P and 16-bit output: 2^-8 (bf16) / 2^-11 (fp16) of the row's largest output, every row, incl. the crafted ones
     tol = 6e-3 if dt == "bf16" else 1e-3
     assert rel.max() < tol, (int(rel.argmax()), rel.max().item())
@@ -304,6 +302,36 @@ def test_encoder_on_the_previous_attention_kernel_agrees(vits):
     d = float((a - b).norm() / b.norm())
     print("attention6 vs attention4 encoders: rel", d)
     assert d < 2e-4, d
+
+
+@pytest.mark.parametrize("path", ["v6", "v4", "split"])
+def test_one_key_tile_frames_through_the_encoder(vits, path):
+    """56 x 70 at stride 7: 7 x 9 patches + CLS = 64 tokens = exactly ONE 64-key tile with no masked tail (every other encoder test
+    has at least four key tiles and a partial last one; the stage alone: tests/test_gpu_vit_attention_shapes.py), and every GEMM at 64
+    rows per frame; two frames.  The default attention kernel and attention_v4 against the fp32 oracle at _check's default bounds,
+    precision="split" against the float64 oracle at the bounds of test_gpu_precision.py::test_split_precision_is_fp32_grade."""
+    sd, ex = vits
+    video = synth.synth_video(2, 56, 70, seed=85)
+    if path == "split":
+        ex = VitExtractor("dinov2_vits14", stride=7, device="cuda:0", state_dict=sd, precision="split")
+    elif path == "v4":
+        ex = VitExtractor("dinov2_vits14", stride=7, device="cuda:0", state_dict=sd)
+        ex.attention_v4 = True
+    feat = ex.encode(video, layer=1)
+    assert feat.shape == (2, 7 * 9, 384) and torch.isfinite(feat).all()
+    for t in range(2):
+        if path == "split":
+            ref = A.vit_tokens(video[t:t + 1].double(), {k: v.double() for k, v in sd.items()}, "dinov2_vits14",
+                               layer=1).permute(1, 2, 0).reshape(-1, 384)
+            got = feat[t].double().cpu()
+            rel = ((got - ref).norm() / ref.norm()).item()
+            tok_rel = ((got - ref).norm(dim=-1) / ref.norm(dim=-1)).max().item()
+            print(f"64 tokens, split, frame {t}: rel {rel:.2e}, worst token {tok_rel:.2e}")
+            assert rel < 2e-6 and tok_rel < 4e-6, (rel, tok_rel)
+        else:
+            ref = A.vit_tokens(video[t:t + 1], sd, "dinov2_vits14", layer=1).permute(1, 2, 0).reshape(-1, 384)
+            cos, rel = _check(feat[t], ref)
+            print(f"64 tokens, {path}, frame {t}: min cos {cos:.7f}, rel {rel:.2e}")
 
 
 # ---- operand types and the fp16 range ---------------------------------------------------------------------------------

@@ -16,6 +16,7 @@ import sys
 import pytest
 import torch
 
+import vit_attention_ref as R
 from dino_tracker_amd import ops, synth
 from dino_tracker_amd._lib import OPERAND_BF16, OPERAND_F16, check, lib
 from dino_tracker_amd.extractor import VitExtractor
@@ -74,14 +75,11 @@ def test_attention_stage_on_split_operands(dt):
     # the operands the device actually saw: hi + lo
     qd, kd, vd = [(planes[2 * i].double() + planes[2 * i + 1].double()).cpu() for i in range(3)]
     vd = vd.transpose(2, 3)
-    s = qd[:, :, :S] @ kd[:, :, :S].transpose(2, 3)
-    p = torch.softmax(s * 0.6931471805599453, dim=-1)
-    ref = (p @ vd[:, :, :S]).permute(0, 2, 1, 3).reshape(F, S, Hh * 64)
+    s = R.scores(qd, kd, S)
+    ref = R.reference(qd, kd, vd, S)
     got = (oh.double() + ol.double()).cpu()
     assert torch.isfinite(got).all()
-    err = (got - ref).abs().amax(dim=-1)
-    scale = ref.abs().amax(dim=-1).clamp(min=0.05)
-    relrow = err / scale
+    relrow = R.row_rel(got, ref)
     rel = relrow.max().item()
     top = torch.topk(relrow.flatten(), 5)
     print(f"split attention {dt}: max row-relative error {rel:.2e} (median {relrow.median().item():.2e}; worst rows (frame * S + query) "
