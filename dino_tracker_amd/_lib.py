@@ -281,6 +281,8 @@ SIGNATURES = {
     "dtk_jpeg_decode_coefficients_sampled": (c_int, [c_int, c_void_p, ctypes.c_int64, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int,
                                                      c_int, c_void_p, c_void_p, c_void_p]),
     "dtk_jpeg_pixels_sampled": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dtk_jpeg_decode_progressive": (c_int, [c_int, c_void_p, ctypes.c_int64, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int,
+                                            c_int, c_void_p, c_void_p, c_void_p]),
     "dtk_inflate": (c_int, [c_void_p, ctypes.c_int64, c_void_p, c_void_p, c_int, c_int, c_void_p, ctypes.c_int64, c_void_p, c_void_p]),
     "dtk_adler32": (c_int, [c_void_p, ctypes.c_int64, c_void_p, c_void_p, c_int, c_void_p, ctypes.c_int64, c_void_p, c_void_p]),
     "dtk_png_unfilter_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),

@@ -202,3 +202,233 @@ JPG_HD int jpg_decode_mcus(JpgBits& b, const JpgHuff* tab, int B, int nm, int16_
     }
     return 0;
 }
+
+// ---- progressive files (SOF2; docs/JPEG_DECODE.md, "Progressive files"; T.81 Annex G) -----------------------------------------------
+// A scan codes the band [Ss, Se] of the zigzag coefficients of its blocks at bit position Al: DC bands (Ss = Se = 0) of one component
+// or of all three interleaved, AC bands (Ss >= 1) of one component.  Ah = 0: the band's first scan; Ah > 0: a refinement that adds
+// bit Al.  The four per-block routines below take the block's 64 coefficients `out` and touch out[Ss .. Se] only.  What holds
+// whatever the bytes and the tables contain:
+//   * every loop iteration consumes at least one bit, advances the coefficient index or ends the block; `iters` counts one per
+//     block, one per symbol and one per coefficient position visited: at most JPG_PROG_ITERS_PER_BLOCK per block, so a segment of
+//     n blocks takes at most 8 * bytes + JPG_PROG_ITERS_PER_BLOCK * n;
+//   * an index beyond Se, or an end-of-band run longer than the `left` blocks of the segment, ends the block with JPG_S_INDEX;
+//   * a refinement symbol whose size is neither 0 nor 1 ends it with JPG_S_CODE.
+constexpr int JPG_PROG_ITERS_PER_BLOCK = 130;
+constexpr int JPG_PROG_FIELDS = 14;   // a row of the segment table (DTK_JPEG_PROG_FIELDS in dtk.h)
+constexpr int JPG_PROG_MAX_AL = 13;
+constexpr int JPG_PROG_MAX_LEVEL = 255;
+
+struct JpgScan {
+    int Ss, Se, Ah, Al;
+    int comp;   // the scan's component, -1: the interleaved DC scan of all three
+};
+
+// one bit; JPG_S_OVERRUN past the end
+JPG_HD int jpg_bit(JpgBits& b, int& status) {
+    const uint32_t w = jpg_window(b, status);
+    if (status) return 0;
+    jpg_consume(b, 1);
+    return (int)(w >> 31);
+}
+
+JPG_HD int jpg_prog_dc_first(JpgBits& b, const JpgHuff& dc, int& pred, int Al, int16_t* out, uint32_t& iters) {
+    int status = 0, sym = 0;
+    ++iters;
+    const uint32_t w = jpg_window(b, status);
+    const int len = jpg_symbol(dc, w, sym);
+    if (status) return status;
+    if (len == 0 || sym > 11) return JPG_S_CODE;
+    pred = (int16_t)(pred + jpg_extend(w, len, sym));   // wraps to 16 bits, as in jpg_decode_block
+    jpg_consume(b, len + sym);
+    out[0] = (int16_t)((uint32_t)pred << Al);
+    return 0;
+}
+
+JPG_HD int jpg_prog_dc_refine(JpgBits& b, int Al, int16_t* out, uint32_t& iters) {
+    int status = 0;
+    ++iters;
+    if (jpg_bit(b, status)) out[0] = (int16_t)(out[0] | (1 << Al));
+    return status;
+}
+
+// an end-of-band symbol of category r behind the `len`-bit code at the top of w: the run's length, this block included
+JPG_HD uint32_t jpg_prog_run(JpgBits& b, uint32_t w, int len, int r) {
+    const uint32_t run = (1u << r) + (r ? (w << len) >> (32 - r) : 0u);
+    jpg_consume(b, len + r);   // at most 16 + 14
+    return run;
+}
+
+// `run`: the blocks of a pending end-of-band run, this one included (0: none); `left`: the blocks left in the segment, this one
+// included
+JPG_HD int jpg_prog_ac_first(JpgBits& b, const JpgHuff& ac, int Ss, int Se, int Al, uint32_t& run, uint32_t left, int16_t* out,
+                             uint32_t& iters) {
+    int status = 0, sym = 0;
+    ++iters;
+    if (run) {
+        --run;   // the block consumes no bits
+        return 0;
+    }
+    int k = Ss;
+    while (k <= Se) {
+        ++iters;
+        const uint32_t w = jpg_window(b, status);
+        if (status) return status;
+        const int len = jpg_symbol(ac, w, sym);
+        if (len == 0) return JPG_S_CODE;
+        const int r = sym >> 4, s = sym & 15;
+        if (s) {
+            k += r;
+            if (k > Se) return JPG_S_INDEX;
+            jpg_consume(b, len + s);   // at most 16 + 15
+            out[k++] = (int16_t)((uint32_t)jpg_extend(w, len, s) << Al);
+        } else if (r == 15) {
+            jpg_consume(b, len);
+            k += 16;
+            if (k > Se) return JPG_S_INDEX;
+        } else {
+            run = jpg_prog_run(b, w, len, r);
+            if (run > left) {
+                run = 0;
+                return JPG_S_INDEX;
+            }
+            --run;
+            break;
+        }
+    }
+    return 0;
+}
+
+// a correction bit for the already non-zero out[k]
+JPG_HD void jpg_prog_correct(JpgBits& b, int Al, int16_t* out, int k, int& status) {
+    if (jpg_bit(b, status) && !(out[k] & (1 << Al))) out[k] = (int16_t)(out[k] + (out[k] > 0 ? (1 << Al) : -(1 << Al)));
+}
+
+JPG_HD int jpg_prog_ac_refine(JpgBits& b, const JpgHuff& ac, int Ss, int Se, int Al, uint32_t& run, uint32_t left, int16_t* out,
+                              uint32_t& iters) {
+    int status = 0, sym = 0;
+    ++iters;
+    int k = Ss;
+    if (run == 0) {
+        while (k <= Se) {
+            ++iters;
+            const uint32_t w = jpg_window(b, status);
+            if (status) return status;
+            const int len = jpg_symbol(ac, w, sym);
+            if (len == 0) return JPG_S_CODE;
+            int r = sym >> 4;
+            const int s = sym & 15;
+            int value = 0;
+            if (s) {
+                if (s != 1) return JPG_S_CODE;
+                jpg_consume(b, len);
+                value = jpg_bit(b, status) ? (1 << Al) : -(1 << Al);
+                if (status) return status;
+            } else if (r == 15) {
+                jpg_consume(b, len);
+            } else {
+                run = jpg_prog_run(b, w, len, r);
+                if (run > left) {
+                    run = 0;
+                    return JPG_S_INDEX;
+                }
+                break;
+            }
+            // pass r still-zero positions, correcting what is non-zero on the way; stop AT the next still-zero one
+            for (; k <= Se; ++k) {
+                ++iters;
+                if (out[k]) {
+                    jpg_prog_correct(b, Al, out, k, status);
+                    if (status) return status;
+                } else if (--r < 0) {
+                    break;
+                }
+            }
+            if (k > Se) return JPG_S_INDEX;
+            if (value) out[k] = (int16_t)value;
+            ++k;
+        }
+    }
+    if (run) {
+        for (; k <= Se; ++k) {
+            ++iters;
+            if (out[k]) {
+                jpg_prog_correct(b, Al, out, k, status);
+                if (status) return status;
+            }
+        }
+        --run;
+    }
+    return 0;
+}
+
+// the real block grid of component c (0: luma) of an H x W picture: what a one-component scan walks
+JPG_HD constexpr int jpg_comp_block_cols(int S, int c, int W) {
+    return c == 0 || S == JPG_444 ? (W + 7) / 8 : ((W + 1) / 2 + 7) / 8;
+}
+JPG_HD constexpr int jpg_comp_block_rows(int S, int c, int H) { return c == 0 || S != JPG_420 ? (H + 7) / 8 : ((H + 1) / 2 + 7) / 8; }
+JPG_HD constexpr long long jpg_mcus(int S, int H, int W) {
+    return (long long)((H + jpg_mcu_height(S) - 1) / jpg_mcu_height(S)) * ((W + jpg_mcu_width(S) - 1) / jpg_mcu_width(S));
+}
+// the units a scan's restart segments count: MCUs for the interleaved scan, the component's real blocks otherwise
+JPG_HD constexpr long long jpg_scan_units(int S, int comp, int H, int W) {
+    return comp < 0 ? jpg_mcus(S, H, W) : (long long)jpg_comp_block_rows(S, comp, H) * jpg_comp_block_cols(S, comp, W);
+}
+
+// where block i of a segment that starts at unit u0 lies in the frame's MCU-major layout [MCUs][B][64]: its block index.  The
+// interleaved scan's blocks follow the layout; block u of a one-component scan is (u / cols, u % cols) of the component's grid.
+JPG_HD long long jpg_scan_block(int S, int comp, long long u0, long long i, int W) {
+    const int B = jpg_blocks_per_mcu(S);
+    if (comp < 0) return u0 * B + i;
+    const long long u = u0 + i;
+    const int cols = jpg_comp_block_cols(S, comp, W), mw = (W + jpg_mcu_width(S) - 1) / jpg_mcu_width(S);
+    const long long by = u / cols;
+    const int bx = (int)(u - by * cols);
+    if (comp > 0) return (by * mw + bx) * B + (B - 3 + comp);
+    const int h = jpg_mcu_width(S) / 8, v = jpg_mcu_height(S) / 8;
+    return ((by / v) * mw + bx / h) * B + (by % v) * h + bx % h;
+}
+
+// A row of the segment table (dtk.h: frame, byte offset, byte length, level, Ss, Se, Ah, Al, component, first unit, units, three
+// table indices) against the stream, the frame count, the sampling's unit counts and the table count.  The library checks the host
+// copy before it launches anything, the kernel its device copy.
+JPG_HD bool jpg_prog_row_ok(const long long* g, int S, int F, int H, int W, long long stream_bytes, int n_tables, long long max_bytes) {
+    if (g[0] < 0 || g[0] >= F || g[1] < 0 || g[2] < 0 || g[2] > max_bytes || g[1] > stream_bytes - g[2]) return false;
+    if (g[3] < 0 || g[3] > JPG_PROG_MAX_LEVEL) return false;
+    const long long Ss = g[4], Se = g[5], Ah = g[6], Al = g[7], comp = g[8];
+    if (Ss < 0 || Se < Ss || Se > 63 || (Ss == 0 && Se != 0) || Al < 0 || Al > JPG_PROG_MAX_AL || (Ah != 0 && Ah != Al + 1)) return false;
+    if (comp < -1 || comp >= jpg_components(S) || (comp < 0 && (Ss != 0 || S == JPG_GRAY))) return false;
+    const long long units = jpg_scan_units(S, (int)comp, H, W);
+    if (g[9] < 0 || g[10] < 1 || g[9] > units - g[10]) return false;
+    const int used = Ss == 0 ? (Ah ? 0 : comp < 0 ? 3 : 1) : 1;
+    for (int t = 0; t < used; ++t)
+        if (g[11 + t] < 0 || g[11 + t] >= n_tables) return false;
+    return true;
+}
+
+// The blocks of one restart segment of a scan from a reader that holds ALL of its bits, into the frame's coefficients `coef`
+// ([MCUs][B][64]; zero before the frame's first scan).  tab: the DC look-up per component of a DC first scan (tab[0] alone when the
+// scan has one component), the AC look-up of an AC scan, unused by a DC refinement.  Predictors and the pending run start at zero.
+// Stops at the first block that reports a status and returns it.  (The kernel runs the same routines around its staging of the bytes
+// and of the coefficients.)
+JPG_HD int jpg_decode_scan_segment(JpgBits& b, const JpgHuff* tab, int S, const JpgScan& sc, long long u0, long long nu, int W,
+                                   int16_t* coef, uint32_t& iters) {
+    const int B = jpg_blocks_per_mcu(S);
+    const long long n = sc.comp < 0 ? nu * B : nu;
+    int pred[3] = {0, 0, 0}, k = 0;
+    uint32_t run = 0;
+    for (long long i = 0; i < n; ++i) {
+        int16_t* out = coef + jpg_scan_block(S, sc.comp, u0, i, W) * 64;
+        const uint32_t left = (uint32_t)(n - i < 0x7fffffffll ? n - i : 0x7fffffffll);
+        int st;
+        if (sc.Ss == 0) {
+            const int c = sc.comp < 0 ? jpg_block_component(B, k) : 0;
+            st = sc.Ah ? jpg_prog_dc_refine(b, sc.Al, out, iters) : jpg_prog_dc_first(b, tab[c], pred[c], sc.Al, out, iters);
+            if (++k == B) k = 0;
+        } else {
+            st = sc.Ah ? jpg_prog_ac_refine(b, tab[0], sc.Ss, sc.Se, sc.Al, run, left, out, iters)
+                       : jpg_prog_ac_first(b, tab[0], sc.Ss, sc.Se, sc.Al, run, left, out, iters);
+        }
+        if (st) return st;
+    }
+    return 0;
+}

@@ -953,6 +953,39 @@ def jpeg_pixels(coef: torch.Tensor, qtables: torch.Tensor, H: int, W: int, statu
     return out
 
 
+JPEG_PROG_FIELDS = 14     # DTK_JPEG_PROG_FIELDS
+
+
+def jpeg_decode_progressive(stream: torch.Tensor, segments, tables: torch.Tensor, frames: int, H: int, W: int,
+                            sampling: int = JPEG_420) -> Tuple[torch.Tensor, torch.Tensor]:
+    """dtk_jpeg_decode_progressive (csrc/jpeg_progressive.hip): stream uint8 [bytes] (device), segments int64 [S, 14] (a HOST array,
+    the rows dtk.h documents, ordered by level -- checked on the host, uploaded here), tables uint8 [N, 272] (device: the raw
+    Huffman tables the rows name) -> (int16 [F, MCUs, B, 64] zigzag, int32 status [F]), the layout jpeg_pixels takes."""
+    import numpy as np
+    B, _, _, _ = jpeg_geometry(sampling)
+    seg = np.ascontiguousarray(np.asarray(segments, dtype=np.int64))
+    if seg.ndim != 2 or seg.shape[1] != JPEG_PROG_FIELDS or seg.shape[0] < 1:
+        raise RuntimeError(f"dino_tracker_amd: segments must be int64 [S, {JPEG_PROG_FIELDS}] with S >= 1, got {seg.shape}")
+    if tables.dim() != 2 or tables.shape[0] < 1 or tables.shape[1] != JPEG_HUFF_BYTES:
+        raise RuntimeError(f"dino_tracker_amd: tables must be uint8 [N, {JPEG_HUFF_BYTES}] with N >= 1, got {tuple(tables.shape)}")
+    if stream.dim() != 1 or stream.numel() == 0:
+        raise RuntimeError(f"dino_tracker_amd: stream must be uint8 [bytes], got {tuple(stream.shape)}")
+    F, H, W = int(frames), int(H), int(W)
+    if F < 1:
+        raise RuntimeError(f"dino_tracker_amd: frames must be positive, got {F}")
+    mcus = jpeg_mcus(H, W, sampling)
+    dev = stream.device
+    if tables.device != dev:
+        raise RuntimeError(f"dino_tracker_amd: tables are on {tables.device}, the stream on {dev}")
+    coef = torch.empty((F, mcus, B, 64), dtype=torch.int16, device=dev)
+    status = torch.empty(F, dtype=torch.int32, device=dev)
+    seg_dev = torch.from_numpy(seg).to(dev)
+    check(lib().dtk_jpeg_decode_progressive(int(sampling), _p(stream, torch.uint8), int(stream.numel()), _p(seg_dev), seg.ctypes.data,
+                                            int(seg.shape[0]), _p(tables, torch.uint8), int(tables.shape[0]), F, H, W, _p(coef),
+                                            _p(status), _stream()))
+    return coef, status
+
+
 # ---- PNG ingest (csrc/inflate.hip): zlib / DEFLATE streams, their Adler-32, the PNG row filters; the chunk parser is png_in's --------
 INFLATE_STREAM_FIELDS = 4
 (INFLATE_S_HEADER, INFLATE_S_BTYPE, INFLATE_S_STORED, INFLATE_S_TABLE, INFLATE_S_CODE, INFLATE_S_DISTANCE, INFLATE_S_OVERRUN,

@@ -8,10 +8,15 @@ decoder for the files an encoder makes).  The host only reads headers:
     decode_jpeg(files_or_bytes, device)       uint8 [T, H, W, 3] on the device, [T, H, W, 1] for gray files
     decode_jpeg_coefficients(...)             the entropy stage alone: (int16 [T, MCUs, B, 64] zigzag, int32 status [T], plan)
 
+    parse_jpeg_progressive(data), scan_levels(scans), plan_jpeg_progressive(datas), decode_jpeg_progressive(...),
+    decode_jpeg_progressive_coefficients(...)  the same for PROGRESSIVE files (SOF2), through their own entry points only
+
 Decoded on the device: baseline sequential (SOF0), 8 bit, ONE scan (Ss = 0, Se = 63, Ah = Al = 0) of either components 1, 2, 3
 interleaved and sampled 2x2 / 1x1 / 1x1 (4:2:0), 2x1 / 1x1 / 1x1 (4:2:2) or 1x1 / 1x1 / 1x1 (4:4:4), or of one component with id 1
 (gray, whatever sampling factors its SOF names); 8-bit quantisation tables, any Huffman tables, any restart interval; an Adobe APP14
-segment only on three components and only with transform 1 (YCbCr).  Everything else -- and every file whose header this parser
+segment only on three components and only with transform 1 (YCbCr).  Progressive files (SOF2) of the same
+layouts with a legal and complete scan script are decoded by the *_progressive functions (further down) and by none of the others.
+Everything else -- and every file whose header this parser
 cannot follow -- is reported with its reason and stays with the caller's host path."""
 from __future__ import annotations
 
@@ -340,3 +345,342 @@ def decode_jpeg(sources: Sequence[Source], device="cuda:0", fallback: bool = Tru
     raises what Pillow raises.  with_status: also the int32 [T] status as the device reported it (host tensor)."""
     pinned, views, plan = _planned(sources)
     return decode_planned(pinned, views, plan, device, fallback, with_status)
+
+
+# ---- progressive files (SOF2): docs/JPEG_DECODE.md "Progressive files", csrc/jpeg_progressive.hip --------------------------------------
+# Decoded on the device when asked for (decode_jpeg_progressive, DTK_JPEG_DECODE=device): 8 bit, components 1 2 3 with one of the
+# three samplings above or one component, 8-bit quantisation tables before the first scan, Huffman coding, a legal and COMPLETE scan
+# script.  parse_jpeg / parse_jpeg_sampled / plan_jpeg* / decode_jpeg keep refusing such files.
+PROG_FIELDS = ops.JPEG_PROG_FIELDS
+PROG_MAX_AL = 13
+
+
+@dataclass
+class JpegScan:
+    components: Tuple[int, ...]  # indices into the frame's components (0: Y), in scan order: one, or (0, 1, 2) interleaved
+    ss: int
+    se: int
+    ah: int
+    al: int
+    tables: Tuple[bytes, ...]    # the raw tables (272 bytes each) in force at the SOS: a DC first scan's DC table per component, an AC
+    #                              scan's AC table, nothing for a DC refinement
+    restart: int                 # the restart interval in force at the SOS, in units; 0: none
+    segments: np.ndarray         # int64 [S, 4]: byte offset in the file, byte length, first unit, units -- a unit is an MCU of an
+    #                              interleaved scan and a block of the component's real grid otherwise
+
+
+@dataclass
+class JpegProgressiveHeader:
+    height: int
+    width: int
+    sampling: int
+    qtables: np.ndarray          # uint8 [C, 64], zigzag order
+    scans: List[JpegScan]
+    adobe: bool = False
+
+    @property
+    def mcus(self) -> int:
+        return mcus_of(self.height, self.width, self.sampling)
+
+
+def scan_units(height: int, width: int, sampling: int, components: Sequence[int]) -> int:
+    """what a scan's restart interval counts: the MCUs of an interleaved scan, else the blocks of the component's REAL grid,
+    ceil(ceil(H v_c / v_max) / 8) rows of ceil(ceil(W h_c / h_max) / 8)"""
+    if len(components) > 1:
+        return mcus_of(height, width, sampling)
+    _, _, mh, mw = ops.jpeg_geometry(sampling)
+    if components[0] == 0:
+        return -(-height // 8) * -(-width // 8)
+    return -(-(-(-height // (mh // 8))) // 8) * -(-(-(-width // (mw // 8))) // 8)
+
+
+def scan_levels(scans: Sequence) -> List[int]:
+    """Scans i < j conflict when they share a component and their bands [ss, se] intersect: j reads or overwrites what i wrote.
+    level(j) = 1 + the highest level among the earlier scans it conflicts with, 0 when there is none: scans of one level touch
+    disjoint coefficients and may be decoded at the same time.  `scans`: objects with components, ss, se (JpegScan)."""
+    levels: List[int] = []
+    for j, b in enumerate(scans):
+        level = 0
+        for i in range(j):
+            a = scans[i]
+            if set(a.components) & set(b.components) and a.ss <= b.se and b.ss <= a.se:
+                level = max(level, levels[i] + 1)
+        levels.append(level)
+    return levels
+
+
+def parse_jpeg_progressive(data) -> Tuple[Optional[JpegProgressiveHeader], Optional[str]]:
+    """Walk SOI .. EOI of one progressive file.  (header, None) when the device decodes it, else (None, why): not SOF2, a layout
+    parse_jpeg_sampled would refuse in a baseline file too, a table or marker the walk cannot follow, a DQT behind the first SOS, an
+    illegal succession of scans, or an INCOMPLETE progression (libjpeg smooths those: other pixels).  A DRI may stand before any
+    SOS and holds from there on -- encoders that count the interval in rows write one per scan."""
+    buf = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data
+    n = int(buf.shape[0])
+    if n < 4 or buf[0] != 0xFF or buf[1] != 0xD8:
+        return None, "no SOI marker"
+    # every FF that is not followed by 00: the markers, inside and outside the entropy-coded data
+    marks = np.flatnonzero((buf[:-1] == 0xFF) & (buf[1:] != 0))
+    dqt, dht, restart, sof, adobe = {}, {}, 0, None, None
+    scans: List[JpegScan] = []
+    geometry = None              # (height, width, ncomp, sampling, component ids' tables) once the SOF is read
+    progress = None              # int [C, 64]: the Al each coefficient has reached, -1: not coded yet
+    i = 2
+    while True:
+        if i + 2 > n or buf[i] != 0xFF:
+            return None, f"no marker at byte {i}"
+        marker = int(buf[i + 1])
+        if marker == 0xFF:          # a fill byte
+            i += 1
+            continue
+        if marker == 0xD9:
+            break
+        if marker == 0xC0:
+            return None, "not progressive (baseline, SOF0)"
+        if marker in _SOF_OTHERS and marker != 0xC2:
+            return None, _SOF_OTHERS[marker]
+        if marker == 0x01 or 0xD0 <= marker <= 0xD8 or marker == 0x00:
+            return None, f"marker FF{marker:02X} between the segments"
+        if i + 4 > n:
+            return None, f"no marker at byte {i}"
+        length = (int(buf[i + 2]) << 8) | int(buf[i + 3])
+        if length < 2 or i + 2 + length > n:
+            return None, f"segment FF{marker:02X} at byte {i} runs past the file"
+        seg = bytes(buf[i + 4:i + 2 + length])
+        i += 2 + length
+        if marker == 0xDB:
+            if scans:
+                return None, "a DQT behind the first SOS"
+            k = 0
+            while k < len(seg):
+                if seg[k] >> 4:
+                    return None, "16-bit quantisation table"
+                if (seg[k] & 15) > 3 or k + 65 > len(seg):
+                    return None, "DQT: table id above 3, or the segment is short"
+                dqt[seg[k] & 15] = np.frombuffer(seg[k + 1:k + 65], dtype=np.uint8)
+                k += 65
+        elif marker == 0xC4:
+            k = 0
+            while k < len(seg):
+                if k + 17 > len(seg) or (seg[k] >> 4) > 1 or (seg[k] & 15) > 3:
+                    return None, "DHT: table class above 1, id above 3, or the segment is short"
+                counts = list(seg[k + 1:k + 17])
+                vals = seg[k + 17:k + 17 + sum(counts)]
+                why = _check_huffman(seg[k] >> 4, counts, vals)      # an AC symbol (r << 4) with r <= 14 is an end-of-band run here
+                if why:
+                    return None, why
+                raw = bytes(counts) + vals
+                dht[seg[k]] = raw + bytes(HUFF_BYTES - len(raw))
+                k += 17 + sum(counts)
+        elif marker == 0xDD:
+            if len(seg) != 2:
+                return None, "DRI: wrong length"
+            restart = (seg[0] << 8) | seg[1]
+        elif marker == 0xEE:
+            if seg[:5] == b"Adobe":
+                adobe = seg[11] if len(seg) >= 12 else -1
+        elif marker == 0xC2:
+            if sof is not None:
+                return None, "two SOF2 segments"
+            sof = seg
+            if len(sof) < 6:
+                return None, "SOF2 is short"
+            if sof[0] != 8:
+                return None, f"{sof[0]}-bit samples"
+            height, width, ncomp = (sof[1] << 8) | sof[2], (sof[3] << 8) | sof[4], sof[5]
+            if ncomp not in (1, 3) or len(sof) != 6 + 3 * ncomp:
+                return None, f"{ncomp} components"
+            if height < 1 or width < 1:
+                return None, "zero height or width (DNL)"
+            comps = [(sof[6 + 3 * c], sof[7 + 3 * c], sof[8 + 3 * c]) for c in range(ncomp)]
+            if [c[0] for c in comps] != [1, 2, 3][:ncomp]:
+                return None, f"component ids {[c[0] for c in comps]}, not {'1 2 3' if ncomp == 3 else '1'}"
+            factors = tuple(c[1] for c in comps)
+            if ncomp == 1:
+                sampling = GRAY
+            elif factors in _FACTORS:
+                sampling = _FACTORS[factors]
+            else:
+                return None, f"sampling {_FACTOR_NAMES.get(factors, [hex(v) for v in factors])}, not 4:2:0, 4:2:2 or 4:4:4"
+            geometry = (height, width, ncomp, sampling, [c[2] for c in comps])
+            progress = np.full((ncomp, 64), -1, dtype=np.int64)
+        elif marker == 0xDA:
+            if geometry is None:
+                return None, "no SOF2 segment before the scan"
+            height, width, ncomp, sampling, _ = geometry
+            ns = seg[0] if seg else 0
+            if ns < 1 or len(seg) != 4 + 2 * ns:
+                return None, "SOS: wrong length"
+            ids = [seg[1 + 2 * c] for c in range(ns)]
+            ss, se, ah, al = seg[1 + 2 * ns], seg[2 + 2 * ns], seg[3 + 2 * ns] >> 4, seg[3 + 2 * ns] & 15
+            which = len(scans)
+            if ns == 1:
+                if not 1 <= ids[0] <= ncomp:
+                    return None, f"scan {which}: component {ids[0]} is not in the frame"
+                components = (ids[0] - 1,)
+            elif ids == [1, 2, 3] and ncomp == 3:
+                components = (0, 1, 2)
+            else:
+                return None, f"scan {which}: components {ids} interleaved, not 1 2 3"
+            if ss > se or se > 63 or (ss == 0 and se != 0):
+                return None, f"scan {which}: band {ss}-{se} is illegal (a DC scan has Ss = Se = 0)"
+            if ss > 0 and ns != 1:
+                return None, f"scan {which}: an AC scan of several components"
+            if al > PROG_MAX_AL:
+                return None, f"scan {which}: Al = {al} above {PROG_MAX_AL}"
+            band = progress[list(components), ss:se + 1]
+            if ah == 0:
+                if (band != -1).any():
+                    return None, f"scan {which}: a first scan (Ah = 0) of coefficients that are coded already"
+            elif (band != ah).any() or al != ah - 1:
+                return None, f"scan {which}: Ah/Al = {ah}/{al} is not the successor of what the band has reached"
+            progress[list(components), ss:se + 1] = al
+            tables: List[bytes] = []
+            if ss == 0 and ah == 0:
+                tables = [dht.get(seg[2 + 2 * c] >> 4) for c in range(ns)]
+            elif ss > 0:
+                tables = [dht.get(0x10 | (seg[2] & 15))]
+            if any(t is None for t in tables):
+                return None, f"scan {which}: a Huffman table is not defined"
+            # the body: FF 00 is data, FF D0 .. D7 split it, any other marker ends it
+            first = int(np.searchsorted(marks, i))
+            k = first
+            while k < marks.size and 0xD0 <= buf[marks[k] + 1] <= 0xD7:
+                k += 1
+            if k == marks.size:
+                return None, f"scan {which}: the file ends inside the scan"
+            end = int(marks[k])
+            at = marks[first:k].astype(np.int64)
+            units = scan_units(height, width, sampling, components)
+            expected = -(-units // restart) - 1 if restart else 0
+            if at.size != expected:
+                return None, f"scan {which}: {at.size} restart markers, {expected} expected"
+            if at.size and not np.array_equal(buf[at + 1] & 7, np.arange(at.size) & 7):
+                return None, f"scan {which}: restart markers out of order"
+            starts = np.concatenate(([i], at + 2)).astype(np.int64)
+            ends = np.concatenate((at, [end])).astype(np.int64)
+            if int((ends - starts).max()) > SEGMENT_MAX_BYTES:
+                return None, "a segment longer than 256 MiB"
+            per = restart if restart else units
+            first_unit = np.arange(starts.size, dtype=np.int64) * per
+            segments = np.stack([starts, ends - starts, first_unit, np.minimum(per, units - first_unit)], axis=1)
+            scans.append(JpegScan(components, ss, se, ah, al, tuple(tables), restart, segments))
+            i = end
+        # COM, APPn and anything else with a length: skipped
+    if geometry is None:
+        return None, "no SOF2 segment"
+    if not scans:
+        return None, "no scan"
+    height, width, ncomp, sampling, tq = geometry
+    if adobe is not None and (ncomp != 3 or adobe != 1):
+        return None, (f"Adobe APP14 segment on {ncomp} component" if ncomp != 3 else
+                      f"Adobe APP14 segment with transform {adobe}, not 1 (YCbCr)" if adobe >= 0 else "Adobe APP14 segment is short")
+    if any(t not in dqt for t in tq):
+        return None, "a component's quantisation table is not defined"
+    if (progress != 0).any():
+        c, k = (int(v[0]) for v in np.nonzero(progress != 0))
+        return None, (f"incomplete progression: coefficient {k} of component {c + 1} " +
+                      ("is never coded" if progress[c, k] < 0 else f"stops at Al = {int(progress[c, k])}"))
+    return JpegProgressiveHeader(height, width, sampling, np.stack([dqt[t] for t in tq]), scans, adobe is not None), None
+
+
+@dataclass
+class JpegProgressivePlan:
+    """what dtk_jpeg_decode_progressive / dtk_jpeg_pixels_sampled take for F progressive files of one size and one sampling"""
+    frames: int
+    height: int
+    width: int
+    segments: np.ndarray   # int64 [S, 14], ordered by level: the rows include/dtk.h documents
+    tables: np.ndarray     # uint8 [N, 272]: every distinct raw Huffman table the rows name
+    qtables: np.ndarray    # uint8 [F, C, 64]
+    sampling: int
+
+
+def plan_jpeg_progressive(datas: Sequence, offsets: Optional[Sequence[int]] = None
+                          ) -> Tuple[Optional[JpegProgressivePlan], Optional[str]]:
+    """Parse every file with parse_jpeg_progressive; (plan, None) when all are eligible and of one size and one sampling, else
+    (None, "file <index>: <reason>").  Every frame may have its own scan script and tables; the levels are scan_levels' per frame."""
+    if not len(datas):
+        return None, "no files"
+    headers: List[JpegProgressiveHeader] = []
+    for f, data in enumerate(datas):
+        h, why = parse_jpeg_progressive(data)
+        if h is None:
+            return None, f"file {f}: {why}"
+        if headers and (h.height, h.width) != (headers[0].height, headers[0].width):
+            return None, f"file {f}: {h.height} x {h.width}, file 0 is {headers[0].height} x {headers[0].width}"
+        if headers and h.sampling != headers[0].sampling:
+            return None, f"file {f}: sampling {SAMPLING_NAMES[h.sampling]}, file 0 is {SAMPLING_NAMES[headers[0].sampling]}"
+        headers.append(h)
+    if offsets is None:
+        offsets = np.concatenate(([0], np.cumsum([len(d) for d in datas])))[:-1]
+    index, rows = {}, []
+    for f, (h, off) in enumerate(zip(headers, offsets)):
+        for scan, level in zip(h.scans, scan_levels(h.scans)):
+            if level > 255:
+                return None, f"file {f}: more than 256 levels of scans"
+            t = [index.setdefault(raw, len(index)) for raw in scan.tables] + [0, 0, 0]
+            r = np.empty((scan.segments.shape[0], PROG_FIELDS), dtype=np.int64)
+            r[:, 0], r[:, 1], r[:, 2], r[:, 3] = f, scan.segments[:, 0] + int(off), scan.segments[:, 1], level
+            r[:, 4:8] = (scan.ss, scan.se, scan.ah, scan.al)
+            r[:, 8] = scan.components[0] if len(scan.components) == 1 else -1
+            r[:, 9:11], r[:, 11:14] = scan.segments[:, 2:4], t[:3]
+            rows.append(r)
+    rows = np.concatenate(rows)
+    rows = np.ascontiguousarray(rows[np.argsort(rows[:, 3], kind="stable")])
+    tables = np.zeros((max(1, len(index)), HUFF_BYTES), dtype=np.uint8)
+    for raw, at in index.items():
+        tables[at] = np.frombuffer(raw, dtype=np.uint8)
+    return JpegProgressivePlan(len(headers), headers[0].height, headers[0].width, rows, tables,
+                               np.stack([h.qtables for h in headers]), headers[0].sampling), None
+
+
+def _planned_progressive(sources: Sequence[Source]) -> Tuple[torch.Tensor, List[np.ndarray], JpegProgressivePlan]:
+    pinned, views = read_pinned(sources)
+    plan, why = plan_jpeg_progressive(views)
+    if plan is None:
+        raise ValueError(f"decode_jpeg_progressive: not decodable on the device -- {why}")
+    return pinned, views, plan
+
+
+def _entropy_progressive(pinned: torch.Tensor, plan: JpegProgressivePlan, device: torch.device):
+    stream = pinned.to(device, non_blocking=True)
+    tables = torch.from_numpy(plan.tables).to(device)
+    return ops.jpeg_decode_progressive(stream, plan.segments, tables, plan.frames, plan.height, plan.width, plan.sampling)
+
+
+def decode_jpeg_progressive_coefficients(sources: Sequence[Source], device="cuda:0"
+                                         ) -> Tuple[torch.Tensor, torch.Tensor, JpegProgressivePlan]:
+    """The entropy stage of progressive files alone: (int16 [T, MCUs, B, 64] zigzag -- decode_jpeg_coefficients' layout: what the
+    baseline file of the same picture holds --, int32 status [T], the plan)."""
+    device = _device(device)
+    pinned, _, plan = _planned_progressive(sources)
+    coef, status = _entropy_progressive(pinned, plan, device)
+    return coef, status, plan
+
+
+def decode_planned_progressive(pinned: torch.Tensor, views: List[np.ndarray], plan: JpegProgressivePlan, device, fallback: bool = True,
+                               with_status: bool = False):
+    """decode_planned for a progressive plan: the scans level by level, then the pixel stage of the baseline decoder, unchanged."""
+    device = _device(device)
+    coef, status = _entropy_progressive(pinned, plan, device)
+    qt = torch.from_numpy(plan.qtables).to(device)
+    out = ops.jpeg_pixels(coef, qt, plan.height, plan.width, status, plan.sampling)
+    mode = "L" if plan.sampling == GRAY else "RGB"
+    if plan.sampling == GRAY:
+        out = out[..., None]
+    host_status = status.cpu()                       # the one host read
+    if fallback and bool(host_status.any()):
+        from PIL import Image
+        for f in torch.nonzero(host_status).flatten().tolist():
+            with Image.open(io.BytesIO(views[f].tobytes())) as img:
+                frame = np.asarray(img.convert(mode) if img.mode != mode else img)
+            out[f] = torch.from_numpy(np.ascontiguousarray(frame).reshape(tuple(out.shape[1:]))).to(device)
+    return (out, host_status) if with_status else out
+
+
+def decode_jpeg_progressive(sources: Sequence[Source], device="cuda:0", fallback: bool = True, with_status: bool = False):
+    """decode_jpeg for PROGRESSIVE files (paths or byte strings) of one size and one sampling: uint8 [T, H, W, 3] -- gray files:
+    [T, H, W, 1] -- on `device`.  ValueError with the reason when a file is not of the kind parse_jpeg_progressive accepts.  The same
+    contract otherwise: ONE host read, the frames' status, and Pillow for a frame whose status is not zero (`fallback`)."""
+    pinned, views, plan = _planned_progressive(sources)
+    return decode_planned_progressive(pinned, views, plan, device, fallback, with_status)

@@ -1,5 +1,5 @@
 """Video ingest on the device: frames are decoded -- baseline 4:2:0 JPEG folders by libdtk (video_in.py, csrc/jpeg_decode.hip:
-the compressed bytes go up; 4:4:4, 4:2:2 and gray ones when DTK_JPEG_DECODE=device asks for it), 8-bit grey or RGB PNG folders by libdtk as well when DTK_PNG_DECODE selects it (png_in.py,
+the compressed bytes go up; 4:4:4, 4:2:2 and gray ones, and progressive files of all four layouts, when DTK_JPEG_DECODE=device asks for it), 8-bit grey or RGB PNG folders by libdtk as well when DTK_PNG_DECODE selects it (png_in.py,
 csrc/inflate.hip), everything else by Pillow on the host and uploaded once as uint8 -- and LANCZOS-resized by libdtk
 (csrc/resize.hip) with Pillow's own 8-bit arithmetic, so the result is bit-equal to `Image.resize(..., Image.LANCZOS)` followed by
 `ToTensor` -- what data/data_utils.py:79-104 (`load_video`) and :47-52 (`resize_tensor_frames_lanczos`) compute on the CPU.
@@ -164,7 +164,8 @@ def _decode_jpeg_device(files, device: torch.device) -> Optional[torch.Tensor]:
     """uint8 [T, H, W, 3] (gray files: [T, H, W, 1]) on the device when every file is a JPEG the device decodes
     (video_in.parse_jpeg_sampled) and all are of one size and one sampling, else None: the routing is decided from the headers, before
     anything is uploaded.  DTK_JPEG_DECODE = host | device | auto (the default): `host` keeps Pillow for everything; `device` takes
-    the device decoder for every eligible folder; `auto` for the eligible folders whose sampling is in JPEG_AUTO_SAMPLINGS."""
+    the device decoder for every eligible folder -- a folder of PROGRESSIVE files that video_in.plan_jpeg_progressive accepts
+    included --; `auto` for the eligible baseline folders whose sampling is in JPEG_AUTO_SAMPLINGS."""
     mode = os.environ.get("DTK_JPEG_DECODE", "auto")
     if mode not in ("auto", "device", "host"):
         raise ValueError(f"DTK_JPEG_DECODE must be auto, device or host, got {mode!r}")
@@ -173,6 +174,11 @@ def _decode_jpeg_device(files, device: torch.device) -> Optional[torch.Tensor]:
     from . import video_in
     pinned, views = video_in.read_pinned(files)
     plan, _ = video_in.plan_jpeg_sampled(views)
+    if plan is None and mode == "device":
+        # a folder of progressive files (video_in.parse_jpeg_progressive): opt-in only, whatever JPEG_AUTO_SAMPLINGS says
+        # (docs/MEASUREMENTS.md "JPEG decode: progressive")
+        progressive, _ = video_in.plan_jpeg_progressive(views)
+        return None if progressive is None else video_in.decode_planned_progressive(pinned, views, progressive, device)
     if plan is None or (mode == "auto" and plan.sampling not in JPEG_AUTO_SAMPLINGS):
         return None
     return video_in.decode_planned(pinned, views, plan, device)
@@ -205,7 +211,7 @@ def load_video(video_folder, resize=None, num_frames: Optional[int] = None, devi
     `num_frames`) as uint8 on the device, LANCZOS-resized to `resize` = (h, w) and converted as ToTensor does -> float32
     [T, C, h, w] on `device`, bit-equal to the host path.  A folder of baseline 4:2:0 JPEG files of one size is decoded on the device
     from its compressed bytes (a frame whose stream is damaged is decoded by Pillow instead) -- with DTK_JPEG_DECODE=device a folder
-    of 4:4:4, 4:2:2 or gray ones as well (_decode_jpeg_device) --, and so is a folder of 8-bit grey or RGB
+    of 4:4:4, 4:2:2 or gray ones, or of progressive files, as well (_decode_jpeg_device) --, and so is a folder of 8-bit grey or RGB
     PNG files of one size when DTK_PNG_DECODE selects the device (decode_png_device; palette, 16-bit, alpha and interlaced files and
     mixed .jpg / .png folders never do); other frames are decoded by Pillow on the host and uploaded once.  Frames that are not all RGB or all L of one size take the host path (train.load_video) and are
     uploaded afterwards."""

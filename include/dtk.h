@@ -1019,6 +1019,37 @@ int dtk_jpeg_decode_coefficients_sampled(int32_t sampling, const uint8_t* stream
 int dtk_jpeg_pixels_sampled(int32_t sampling, const int16_t* coef, const uint8_t* qtables, int32_t F, int32_t H, int32_t W, uint8_t* out,
                             int32_t* status, void* workspace, void* stream);
 
+/* ---- Video ingest: PROGRESSIVE JPEG (SOF2, 8 bit, Huffman, the four samplings above; docs/JPEG_DECODE.md "Progressive files"): the
+ * entropy stage alone.  It fills the coefficient layout of dtk_jpeg_decode_coefficients_sampled, so dtk_jpeg_pixels_sampled follows
+ * unchanged.  The header, the legality and completeness of the scan script and the LEVELS are the caller's
+ * (dino_tracker_amd/video_in.py: parse_jpeg_progressive, scan_levels, plan_jpeg_progressive). ------------------------------------
+ * dtk_jpeg_decode_progressive: a SEGMENT is a restart interval of ONE scan (or the whole scan).  segments / segments_host: int64
+ *   [n_segments][DTK_JPEG_PROG_FIELDS], on the device and the same values on the host, one row per segment:
+ *      0 frame          1 byte offset in stream   2 byte length (<= 2^28)   3 level (0 .. 255)
+ *      4 Ss   5 Se      6 Ah   7 Al               the scan's band and bit positions: Ss = Se = 0 (DC) or 1 <= Ss <= Se <= 63 (AC);
+ *                                                 Al <= 13; Ah = 0 (the band's first scan) or Ah = Al + 1 (a refinement)
+ *      8 component      0 .. C - 1, or -1: the DC scan of all three components interleaved (not for DTK_JPEG_GRAY, DC only)
+ *      9 first unit    10 unit count (>= 1)       a unit is an MCU of the interleaved scan, else one block of the component's REAL
+ *                                                 grid -- ceil(ceil(H v_c / v_max) / 8) rows of ceil(ceil(W h_c / h_max) / 8)
+ *                                                 blocks, in raster order
+ *     11 12 13 tables   rows of `tables`: a DC first scan names its DC table per component (11 alone for one component), an AC scan
+ *                       its AC table in 11; what a scan does not use is ignored
+ *   The rows are ordered by level; all rows of one level are decoded by ONE launch, one wave per row, and the launches follow each
+ *   other on the stream.  Rows of one level must not write the same coefficient of the same block: the caller gives a scan a higher
+ *   level than every earlier scan of the same component whose band intersects its own.  Every host row is checked against
+ *   stream_bytes, F, the unit count that follows from the sampling, the component and H x W, n_tables and the level order BEFORE
+ *   anything is launched (DTK_E_INVALID); the kernel repeats the check on the device copy and sets DTK_JPEG_S_SEGMENT for a row that
+ *   fails it, which decodes nothing.
+ *   tables uint8 [n_tables][DTK_JPEG_HUFF_BYTES]: raw tables as a DHT stores them (validated by the caller; memory-safe for any
+ *   content).  coef int16 [F][mh mw][B][64] and status int32 [F] are ZEROED here first.  Status: the DTK_JPEG_S_* bits above --
+ *   CODE also for a refinement symbol whose size is neither 0 nor 1, INDEX also for a run or skip beyond Se and for an end-of-band
+ *   run longer than the blocks left in the segment.  A segment stops at its first CODE / INDEX / OVERRUN and writes nothing further.
+ *   No host synchronisation inside. */
+#define DTK_JPEG_PROG_FIELDS 14
+int dtk_jpeg_decode_progressive(int32_t sampling, const uint8_t* stream, int64_t stream_bytes, const int64_t* segments,
+                                const int64_t* segments_host, int32_t n_segments, const uint8_t* tables, int32_t n_tables, int32_t F,
+                                int32_t H, int32_t W, int16_t* coef, int32_t* status, void* stream_handle);
+
 /* ---- Video and mask ingest: PNG DECODING (docs/PNG_DECODE.md): zlib / DEFLATE streams, their Adler-32, the PNG row filters.  The
  * file is the CALLER's to parse (dino_tracker_amd/png_in.py: signature, IHDR, PLTE, the IDAT payloads joined into one stream per
  * frame); the library sees byte streams and raw scanlines.  Everything is exact: the format is lossless. ------------------------------
