@@ -281,6 +281,9 @@ SIGNATURES = {
     "dtk_jpeg_decode_coefficients_sampled": (c_int, [c_int, c_void_p, ctypes.c_int64, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int,
                                                      c_int, c_void_p, c_void_p, c_void_p]),
     "dtk_jpeg_pixels_sampled": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dtk_jpeg_decode_parallel_workspace_bytes": (c_size_t, [c_int, ctypes.c_int64, c_int, c_int]),
+    "dtk_jpeg_decode_coefficients_parallel": (c_int, [c_int, c_void_p, ctypes.c_int64, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int,
+                                                      c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "dtk_jpeg_decode_progressive": (c_int, [c_int, c_void_p, ctypes.c_int64, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int,
                                             c_int, c_void_p, c_void_p, c_void_p]),
     "dtk_inflate": (c_int, [c_void_p, ctypes.c_int64, c_void_p, c_void_p, c_int, c_int, c_void_p, ctypes.c_int64, c_void_p, c_void_p]),

@@ -1,7 +1,8 @@
 // jpeg_entropy.h -- the sequential part of baseline-JPEG decoding (docs/JPEG_DECODE.md section 1): Huffman look-ups built from a DHT's
 // raw counts and symbols, an MSB-first bit reader over UNSTUFFED bytes, and the decode loop of one 8 x 8 block.  Plain C++ that
 // compiles for the host and for the device: the kernel in jpeg_decode.hip and the stand-alone host program tests/host/
-// jpeg_entropy_host.cpp (built with the sanitisers) run the same lines.
+// jpeg_entropy_host.cpp (built with the sanitisers) run the same lines.  At the end of the file: the same decoding cut into
+// sub-streams that many lanes work on side by side (section 1b; csrc/jpeg_parallel.hip, tests/host/jpeg_parallel_host.cpp).
 //
 // What holds whatever the bytes and the tables contain (the tables the library is handed are validated by the caller, but nothing
 // below relies on it):
@@ -431,4 +432,195 @@ JPG_HD int jpg_decode_scan_segment(JpgBits& b, const JpgHuff* tab, int S, const 
         if (st) return st;
     }
     return 0;
+}
+
+// ---- decoding inside a segment in parallel (docs/JPEG_DECODE.md section 1b) ----------------------------------------------------------
+// The unstuffed bytes of a baseline segment are cut into SUB-STREAMS of L bytes.  A decoder STATE is (p, c, k): the bit position, the
+// block's place in its MCU, the zigzag index (0: a DC symbol is next).  jpg_step decodes ONE symbol exactly as jpg_decode_block does;
+// a SPECULATIVE step that meets an invalid code, a DC category above 11, an index beyond 63 or the segment's end RECOVERS -- it skips
+// one bit and ends the block -- so the map from a state to the next is total and the chain of entry states from (0, 0, 0) is well
+// defined for any bytes.  What holds whatever the bytes and the tables contain:
+//   * every step, valid or recovering, consumes at least one bit: jpg_advance takes at most `bound - p` steps;
+//   * jpg_write_substream stores only to blocks [0, nb) of the `coef` it is handed and stops at the first status;
+//   * the reader is JpgBits: no word beyond the one after the last valid bit is touched.
+struct JpgState {
+    uint32_t p;   // bit position in the unstuffed segment
+    uint16_t c;   // the block's place in its MCU, 0 .. B - 1
+    uint16_t k;   // zigzag index of the next coefficient; 0: the next symbol is a DC symbol
+};
+JPG_HD unsigned long long jpg_state_pack(const JpgState& s) {
+    return ((unsigned long long)s.p << 32) | ((unsigned long long)s.c << 16) | (unsigned long long)s.k;
+}
+JPG_HD JpgState jpg_state_unpack(unsigned long long v) {
+    JpgState s;
+    s.p = (uint32_t)(v >> 32), s.c = (uint16_t)((v >> 16) & 0xffffu), s.k = (uint16_t)(v & 0xffffu);
+    return s;
+}
+constexpr int JPG_SUBSEQ_DEFAULT = 128, JPG_SUBSEQ_MIN = 16, JPG_SUBSEQ_MAX = 1024;
+JPG_HD constexpr bool jpg_subseq_ok(int L) { return L >= JPG_SUBSEQ_MIN && L <= JPG_SUBSEQ_MAX && L % 4 == 0; }
+
+// One symbol from the reader `b`, which stands at s.p.  idx >= 0: coefficient `idx` of the current block takes `value` (for idx == 0
+// the DC DIFFERENCE).  A strict step returns the status jpg_decode_block would (the state is then meaningless); a speculative step
+// always returns 0.
+JPG_HD int jpg_step(JpgBits& b, const JpgHuff* tab, int B, JpgState& s, bool speculative, int& idx, int& value) {
+    int status = 0, sym = 0, next = 64, fault = 0;
+    idx = -1, value = 0;
+    const bool dc = s.k == 0;
+    const int place = s.c < B ? s.c : 0;
+    const JpgHuff& t = tab[2 * jpg_block_component(B, place) + (dc ? 0 : 1)];
+    const uint32_t w = jpg_window(b, status);
+    const int len = status ? 0 : jpg_symbol(t, w, sym);
+    if (status) {
+        fault = status;
+    } else if (len == 0 || (dc && sym > 11)) {
+        fault = JPG_S_CODE;
+    } else if (dc) {
+        idx = 0, value = jpg_extend(w, len, sym), next = 1;
+        jpg_consume(b, len + sym);
+    } else {
+        const int r = sym >> 4, size = sym & 15;
+        if (size == 0) {
+            next = r != 15 ? 64 : (int)s.k + 16;   // EOB; ZRL (beyond 63 the block ends, as `while (k < 64)` does)
+            jpg_consume(b, len);
+        } else if ((int)s.k + r > 63) {
+            fault = JPG_S_INDEX;
+        } else {
+            idx = (int)s.k + r, value = jpg_extend(w, len, size), next = idx + 1;
+            jpg_consume(b, len + size);
+        }
+    }
+    if (fault) {
+        if (!speculative) return fault;
+        jpg_consume(b, 1);   // the recovery rule: skip one bit (nothing was consumed yet), end the block
+        next = 64;
+    }
+    if (next >= 64) {
+        s.k = 0;
+        s.c = (uint16_t)(place + 1 == B ? 0 : place + 1);
+    } else {
+        s.k = (uint16_t)next;
+    }
+    s.p = b.pos;
+    return 0;
+}
+
+// f: speculative steps from s while s.p < bound.  Returns the number of blocks that START on the way (steps taken at k == 0).
+JPG_HD uint32_t jpg_advance(JpgBits& b, const JpgHuff* tab, int B, JpgState& s, uint32_t bound, uint32_t& iters) {
+    uint32_t starts = 0;
+    int idx, value;
+    while (s.p < bound) {
+        ++iters;
+        starts += s.k == 0 ? 1u : 0u;
+        jpg_step(b, tab, B, s, true, idx, value);
+    }
+    return starts;
+}
+
+// The strict pass of one sub-stream: from its entry state s (the reader stands there) while s.p < bound, with `first` the number of
+// blocks that start before the sub-stream.  Non-zero values go to coef[block * 64 + idx] of the segment's nb blocks (ZEROED by the
+// caller), DC differences to index 0.  The chain stops at the segment's block count: the step that completes block nb - 1 sets
+// `ended` and leaves the bit position behind it in end_pos.  Returns the first status it meets.
+JPG_HD int jpg_write_substream(JpgBits& b, const JpgHuff* tab, int B, JpgState s, uint32_t bound, long long first, long long nb,
+                               int16_t* coef, bool& ended, uint32_t& end_pos, uint32_t& iters) {
+    if (first < 0) first = 0;
+    if (first > nb + 1) first = nb + 1;
+    long long next = first, cur = first - 1;
+    if (s.k != 0 && (cur < 0 || cur >= nb)) return 0;   // inside a block outside the segment: behind its end, or behind an error
+    int idx, value;
+    while (s.p < bound) {
+        if (s.k == 0) {
+            if (next >= nb) return 0;
+            cur = next++;
+        }
+        ++iters;
+        const int st = jpg_step(b, tab, B, s, false, idx, value);
+        if (st) return st;
+        if (idx >= 0 && value != 0 && cur >= 0 && cur < nb) coef[cur * 64 + idx] = (int16_t)value;
+        if (s.k == 0 && next == nb) {
+            ended = true, end_pos = s.p;
+            return 0;
+        }
+    }
+    return 0;
+}
+
+// DC differences -> predictors: per component the running sum over the segment's blocks, wrapping to int16 as jpg_decode_block does
+JPG_HD void jpg_dc_sums(int16_t* coef, long long first, long long count, int B, int (&pred)[3]) {
+    int k = (int)(first % B);
+    for (long long blk = first; blk < first + count; ++blk) {
+        const int comp = jpg_block_component(B, k);
+        pred[comp] = (int16_t)(pred[comp] + coef[blk * 64]);
+        coef[blk * 64] = (int16_t)pred[comp];
+        if (++k == B) k = 0;
+    }
+}
+
+// the end check of the sequential kernel
+JPG_HD int jpg_end_status(uint32_t pos, uint32_t avail_bits) {
+    return pos > avail_bits ? JPG_S_OVERRUN : avail_bits - pos > 7u ? JPG_S_LEFTOVER : 0;
+}
+
+// The redo rule: a segment whose strict pass reported anything is zeroed and decoded by the sequential loop.
+JPG_HD int jpg_decode_segment_sequential(const uint32_t* words, uint32_t avail_bits, const JpgHuff* tab, int B, int nm, int16_t* coef,
+                                         uint32_t& iters) {
+    JpgBits b;
+    jpg_bits_start(b, words, avail_bits, 0u);
+    int st = jpg_decode_mcus(b, tab, B, nm, coef, iters);
+    if (!st) st = jpg_end_status(b.pos, avail_bits);
+    return st;
+}
+
+JPG_HD uint32_t jpg_substreams(uint32_t unstuffed_bytes, int L) { return unstuffed_bytes ? (unstuffed_bytes + (uint32_t)L - 1u) / (uint32_t)L : 1u; }
+
+// The whole of section 1b over one segment, one sub-stream after the other: what the kernel's lanes do side by side.  words: the
+// unstuffed bytes as JpgBits takes them; states, counts: n = jpg_substreams(bytes, L) entries each; coef: nm * B * 64 values, ZEROED.
+// rounds: how often the states were swept (at most n + 1).  Returns the status.
+JPG_HD int jpg_decode_segment_substreams(const uint32_t* words, uint32_t unstuffed_bytes, const JpgHuff* tab, int B, int nm, int L,
+                                         unsigned long long* states, int32_t* counts, int16_t* coef, uint32_t& rounds, uint32_t& iters) {
+    const uint32_t avail = unstuffed_bytes * 8u, n = jpg_substreams(unstuffed_bytes, L);
+    const long long nb = (long long)nm * B;
+    JpgBits b;
+    for (uint32_t i = 0; i < n; ++i) states[i] = (unsigned long long)(8u * (uint32_t)L * i) << 32;   // the guesses; e_0 is known
+    rounds = 0;
+    for (uint32_t round = 0; round <= n; ++round) {   // bounded by the number of sub-streams
+        bool changed = false;
+        ++rounds;
+        for (uint32_t i = 0; i + 1 < n; ++i) {
+            JpgState s = jpg_state_unpack(states[i]);
+            jpg_bits_start(b, words, avail, s.p);
+            for (uint32_t j = i + 1; j < n; ++j) {   // carry the state on until it meets an equal stored one
+                jpg_advance(b, tab, B, s, 8u * (uint32_t)L * j, iters);
+                if (states[j] == jpg_state_pack(s)) break;
+                states[j] = jpg_state_pack(s), changed = true;
+            }
+        }
+        if (!changed) break;
+    }
+    long long total = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        JpgState s = jpg_state_unpack(states[i]);
+        jpg_bits_start(b, words, avail, s.p);
+        const long long c = jpg_advance(b, tab, B, s, i + 1 < n ? 8u * (uint32_t)L * (i + 1u) : avail, iters);
+        counts[i] = (int32_t)(total < nb + 1 ? total : nb + 1);   // the exclusive scan, clamped: beyond nb nothing is decoded
+        total += c;
+    }
+    int st = 0;
+    bool ended = false;
+    uint32_t end_pos = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        const JpgState s = jpg_state_unpack(states[i]);
+        jpg_bits_start(b, words, avail, s.p);
+        st |= jpg_write_substream(b, tab, B, s, i + 1 < n ? 8u * (uint32_t)L * (i + 1u) : 0xffffffffu, counts[i], nb, coef, ended, end_pos,
+                                  iters);
+    }
+    if (!st) {
+        int pred[3] = {0, 0, 0};
+        jpg_dc_sums(coef, 0, nb, B, pred);
+        st = ended ? jpg_end_status(end_pos, avail) : JPG_S_OVERRUN;
+    }
+    if (st) {
+        for (long long i = 0; i < nb * 64; ++i) coef[i] = 0;
+        st = jpg_decode_segment_sequential(words, avail, tab, B, nm, coef, iters);
+    }
+    return st;
 }

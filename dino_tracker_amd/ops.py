@@ -931,6 +931,36 @@ def jpeg_decode_coefficients(stream: torch.Tensor, segments, huffman: torch.Tens
     return coef, status
 
 
+def jpeg_decode_coefficients_parallel(stream: torch.Tensor, segments, huffman: torch.Tensor, H: int, W: int, sampling: int = JPEG_420,
+                                      subseq_bytes: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """dtk_jpeg_decode_coefficients_parallel (csrc/jpeg_parallel.hip): jpeg_decode_coefficients with many lanes per segment -- the
+    same arguments, the same coefficients and status.  subseq_bytes: the sub-stream length, 0 for the library's default, else a
+    multiple of 4 in 16 .. 1024.  The segments' byte ranges must rise with the row index and not overlap."""
+    import numpy as np
+    B, C, _, _ = jpeg_geometry(sampling)
+    seg = np.ascontiguousarray(np.asarray(segments, dtype=np.int64))
+    if seg.ndim != 2 or seg.shape[1] != JPEG_SEGMENT_FIELDS or seg.shape[0] < 1:
+        raise RuntimeError(f"dino_tracker_amd: segments must be int64 [S, {JPEG_SEGMENT_FIELDS}] with S >= 1, got {seg.shape}")
+    if huffman.dim() != 4 or tuple(huffman.shape[1:]) != (C, 2, JPEG_HUFF_BYTES):
+        raise RuntimeError(f"dino_tracker_amd: huffman must be uint8 [F, {C}, 2, {JPEG_HUFF_BYTES}], got {tuple(huffman.shape)}")
+    if stream.dim() != 1 or stream.numel() == 0:
+        raise RuntimeError(f"dino_tracker_amd: stream must be uint8 [bytes], got {tuple(stream.shape)}")
+    F, H, W, L = int(huffman.shape[0]), int(H), int(W), int(subseq_bytes)
+    need = int(lib().dtk_jpeg_decode_parallel_workspace_bytes(int(sampling), int(stream.numel()), int(seg.shape[0]), L))
+    if need == 0:
+        raise RuntimeError(f"dino_tracker_amd: subseq_bytes must be 0 or a multiple of 4 in 16 .. 1024, got {subseq_bytes!r}")
+    mcus = jpeg_mcus(H, W, sampling)
+    dev = stream.device
+    coef = torch.zeros((F, mcus, B, 64), dtype=torch.int16, device=dev)
+    status = torch.empty(F, dtype=torch.int32, device=dev)
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    seg_dev = torch.from_numpy(seg).to(dev)
+    check(lib().dtk_jpeg_decode_coefficients_parallel(int(sampling), _p(stream, torch.uint8), int(stream.numel()), _p(seg_dev),
+                                                      seg.ctypes.data, int(seg.shape[0]), _p(huffman, torch.uint8), F, H, W, L, _p(coef),
+                                                      _p(status), _p(ws), _stream()))
+    return coef, status
+
+
 def jpeg_pixels(coef: torch.Tensor, qtables: torch.Tensor, H: int, W: int, status: Optional[torch.Tensor] = None,
                 sampling: int = JPEG_420) -> torch.Tensor:
     """dtk_jpeg_pixels_sampled: coef int16 [F, MCUs, B, 64], qtables uint8 [F, C, 64] (zigzag) -> uint8 [F, H, W, 3], for JPEG_GRAY

@@ -7,6 +7,8 @@ decoder for the files an encoder makes).  The host only reads headers:
     parse_jpeg(data), plan_jpeg(datas)        the same, for 4:2:0 files without an Adobe segment only
     decode_jpeg(files_or_bytes, device)       uint8 [T, H, W, 3] on the device, [T, H, W, 1] for gray files
     decode_jpeg_coefficients(...)             the entropy stage alone: (int16 [T, MCUs, B, 64] zigzag, int32 status [T], plan)
+    entropy_mode(entropy)                     "sequential" (one lane per segment) or "parallel" (a workgroup per segment: for files
+                                              without restart markers), from the argument or DTK_JPEG_ENTROPY; the frames are the same
 
     parse_jpeg_progressive(data), scan_levels(scans), plan_jpeg_progressive(datas), decode_jpeg_progressive(...),
     decode_jpeg_progressive_coefficients(...)  the same for PROGRESSIVE files (SOF2), through their own entry points only
@@ -295,9 +297,25 @@ def _device(device) -> torch.device:
     return device
 
 
-def _entropy(pinned: torch.Tensor, plan: JpegPlan, device: torch.device):
+ENTROPY_MODES = ("sequential", "parallel")
+
+
+def entropy_mode(entropy: Optional[str] = None) -> str:
+    """The entropy stage to use: `entropy` when given, else DTK_JPEG_ENTROPY, else "sequential" (one lane per segment:
+    ops.jpeg_decode_coefficients).  "parallel": many lanes per segment (ops.jpeg_decode_coefficients_parallel, docs/JPEG_DECODE.md
+    section 1b) -- the same coefficients and status.  ValueError on anything else.  Baseline files only: progressive files do not use it."""
+    mode = os.environ.get("DTK_JPEG_ENTROPY", "sequential") if entropy is None else entropy
+    if mode not in ENTROPY_MODES:
+        raise ValueError(f"the JPEG entropy stage must be one of {ENTROPY_MODES} (argument `entropy` or DTK_JPEG_ENTROPY), got {mode!r}")
+    return mode
+
+
+def _entropy(pinned: torch.Tensor, plan: JpegPlan, device: torch.device, entropy: Optional[str] = None, subseq_bytes: int = 0):
+    mode = entropy_mode(entropy)
     stream = pinned.to(device, non_blocking=True)
     huff = torch.from_numpy(plan.huffman).to(device)
+    if mode == "parallel":
+        return ops.jpeg_decode_coefficients_parallel(stream, plan.segments, huff, plan.height, plan.width, plan.sampling, subseq_bytes)
     return ops.jpeg_decode_coefficients(stream, plan.segments, huff, plan.height, plan.width, plan.sampling)
 
 
@@ -309,19 +327,20 @@ def _planned(sources: Sequence[Source]) -> Tuple[torch.Tensor, List[np.ndarray],
     return pinned, views, plan
 
 
-def decode_jpeg_coefficients(sources: Sequence[Source], device="cuda:0") -> Tuple[torch.Tensor, torch.Tensor, JpegPlan]:
+def decode_jpeg_coefficients(sources: Sequence[Source], device="cuda:0", entropy: Optional[str] = None, subseq_bytes: int = 0
+                             ) -> Tuple[torch.Tensor, torch.Tensor, JpegPlan]:
     """The entropy stage alone: (int16 [T, MCUs, B, 64] in zigzag order -- B = 6, 4, 3, 1 blocks per MCU for 4:2:0, 4:2:2, 4:4:4, gray --,
-    int32 status [T] -- ops.JPEG_S_* bits --, the plan)."""
+    int32 status [T] -- ops.JPEG_S_* bits --, the plan).  entropy, subseq_bytes: entropy_mode."""
     device = _device(device)
     pinned, _, plan = _planned(sources)
-    coef, status = _entropy(pinned, plan, device)
+    coef, status = _entropy(pinned, plan, device, entropy, subseq_bytes)
     return coef, status, plan
 
 
 def decode_planned(pinned: torch.Tensor, views: List[np.ndarray], plan: JpegPlan, device, fallback: bool = True,
-                   with_status: bool = False):
+                   with_status: bool = False, entropy: Optional[str] = None, subseq_bytes: int = 0):
     device = _device(device)
-    coef, status = _entropy(pinned, plan, device)
+    coef, status = _entropy(pinned, plan, device, entropy, subseq_bytes)
     qt = torch.from_numpy(plan.qtables).to(device)
     out = ops.jpeg_pixels(coef, qt, plan.height, plan.width, status, plan.sampling)
     mode = "L" if plan.sampling == GRAY else "RGB"
@@ -337,14 +356,17 @@ def decode_planned(pinned: torch.Tensor, views: List[np.ndarray], plan: JpegPlan
     return (out, host_status) if with_status else out
 
 
-def decode_jpeg(sources: Sequence[Source], device="cuda:0", fallback: bool = True, with_status: bool = False):
+def decode_jpeg(sources: Sequence[Source], device="cuda:0", fallback: bool = True, with_status: bool = False,
+                entropy: Optional[str] = None, subseq_bytes: int = 0):
     """uint8 [T, H, W, 3] -- gray files: [T, H, W, 1] -- on `device` from JPEG files (paths) or byte strings of one size and one
     sampling.  ValueError with the reason when a file
     is not of the kind the device decodes (module docstring).  After the launches ONE host read, the frames' status; a frame
     whose status is not zero -- a damaged stream -- is decoded by Pillow instead and uploaded into its slot (`fallback`), which
-    raises what Pillow raises.  with_status: also the int32 [T] status as the device reported it (host tensor)."""
+    raises what Pillow raises.  with_status: also the int32 [T] status as the device reported it (host tensor).  entropy:
+    "sequential" or "parallel" (default: DTK_JPEG_ENTROPY, else sequential), subseq_bytes: the parallel stage's sub-stream length
+    (entropy_mode) -- the frames are the same either way."""
     pinned, views, plan = _planned(sources)
-    return decode_planned(pinned, views, plan, device, fallback, with_status)
+    return decode_planned(pinned, views, plan, device, fallback, with_status, entropy, subseq_bytes)
 
 
 # ---- progressive files (SOF2): docs/JPEG_DECODE.md "Progressive files", csrc/jpeg_progressive.hip --------------------------------------

@@ -165,7 +165,9 @@ def _decode_jpeg_device(files, device: torch.device) -> Optional[torch.Tensor]:
     (video_in.parse_jpeg_sampled) and all are of one size and one sampling, else None: the routing is decided from the headers, before
     anything is uploaded.  DTK_JPEG_DECODE = host | device | auto (the default): `host` keeps Pillow for everything; `device` takes
     the device decoder for every eligible folder -- a folder of PROGRESSIVE files that video_in.plan_jpeg_progressive accepts
-    included --; `auto` for the eligible baseline folders whose sampling is in JPEG_AUTO_SAMPLINGS."""
+    included --; `auto` for the eligible baseline folders whose sampling is in JPEG_AUTO_SAMPLINGS.  Which entropy stage a baseline
+    folder that goes to the device runs is DTK_JPEG_ENTROPY's business (video_in.entropy_mode): `sequential`, the default, or
+    `parallel` -- for files without restart markers; the frames are the same."""
     mode = os.environ.get("DTK_JPEG_DECODE", "auto")
     if mode not in ("auto", "device", "host"):
         raise ValueError(f"DTK_JPEG_DECODE must be auto, device or host, got {mode!r}")

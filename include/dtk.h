@@ -1019,6 +1019,25 @@ int dtk_jpeg_decode_coefficients_sampled(int32_t sampling, const uint8_t* stream
 int dtk_jpeg_pixels_sampled(int32_t sampling, const int16_t* coef, const uint8_t* qtables, int32_t F, int32_t H, int32_t W, uint8_t* out,
                             int32_t* status, void* workspace, void* stream);
 
+/* dtk_jpeg_decode_coefficients_parallel (csrc/jpeg_parallel.hip; docs/JPEG_DECODE.md section 1b): the entropy stage of
+ *   dtk_jpeg_decode_coefficients_sampled with MANY lanes per segment -- one workgroup per segment, the segment's unstuffed bytes cut
+ *   into sub-streams of subseq_bytes bytes whose entry states are iterated to their fixpoint.  Arguments, coefficients and status are
+ *   those of dtk_jpeg_decode_coefficients_sampled, for any bytes and any tables; what follows (dtk_jpeg_pixels_sampled) is unchanged.
+ *   subseq_bytes: 0 for the default (128), else a multiple of 4 in 16 .. 1024.  workspace:
+ *   dtk_jpeg_decode_parallel_workspace_bytes(sampling, stream_bytes, n_segments, subseq_bytes) bytes, 256-byte aligned: the unstuffed
+ *   bytes, a state and a block count per sub-stream.  A segment's place in it follows from its byte range, so here the rows of
+ *   segments_host must not overlap in bytes and must rise with the row index (what a parser emits); the device copy is to hold the same
+ *   values -- one that does not stays memory-safe (DTK_JPEG_S_SEGMENT where its place would leave the workspace).
+ *   No host synchronisation inside.  Refused with DTK_E_INVALID before anything is launched: what
+ *   dtk_jpeg_decode_coefficients_sampled refuses, a subseq_bytes outside the above, a null workspace, rows whose bytes overlap or
+ *   fall; the workspace size is 0 for such arguments.  Baseline segments only: a progressive scan's refinements depend on earlier
+ *   coefficients. */
+size_t dtk_jpeg_decode_parallel_workspace_bytes(int32_t sampling, int64_t stream_bytes, int32_t n_segments, int32_t subseq_bytes);
+int dtk_jpeg_decode_coefficients_parallel(int32_t sampling, const uint8_t* stream, int64_t stream_bytes, const int64_t* segments,
+                                          const int64_t* segments_host, int32_t n_segments, const uint8_t* huffman, int32_t F, int32_t H,
+                                          int32_t W, int32_t subseq_bytes, int16_t* coef_out, int32_t* status, void* workspace,
+                                          void* stream_handle);
+
 /* ---- Video ingest: PROGRESSIVE JPEG (SOF2, 8 bit, Huffman, the four samplings above; docs/JPEG_DECODE.md "Progressive files"): the
  * entropy stage alone.  It fills the coefficient layout of dtk_jpeg_decode_coefficients_sampled, so dtk_jpeg_pixels_sampled follows
  * unchanged.  The header, the legality and completeness of the scan script and the LEVELS are the caller's
