@@ -46,7 +46,8 @@ class VitModel(ctypes.Structure):
                 ("cls_pos", c_void_p), ("pos", c_void_p), ("mean_std", c_void_p), ("layers", ctypes.POINTER(VitLayer)),
                 ("frame_batch", ctypes.c_int32), ("overflow", c_void_p),
                 ("tap_out", c_void_p), ("tap_mask", ctypes.c_uint64), ("tap_scale", ctypes.c_float),
-                ("ffn", ctypes.c_int32), ("hidden", ctypes.c_int32)]
+                ("ffn", ctypes.c_int32), ("hidden", ctypes.c_int32),
+                ("n_registers", ctypes.c_int32), ("registers", c_void_p)]
 
 
 VIT_TILED_GEMMS, VIT_BF16, VIT_CHECK_RANGE, VIT_GEMM_WS_V1, VIT_ATTENTION_V4, VIT_GEMM_WIDE_V1, VIT_NO_LN_FUSION = 1, 2, 4, 16, 32, 64, 128  # dtk_vit_model.flags (8 is retired)

@@ -1,13 +1,14 @@
 // vit.hip -- P1: DINOv2 ViT encoder as driven by VitExtractor (models/extractor.py:41-150, utils.py:33-72):
 // overlapping patch embedding (14x14, stride 7) of ImageNet-normalised frames + interpolated position encoding,
 // `depth` transformer blocks (LN -> QKV -> MHSA -> proj -> LayerScale -> +res; LN -> fc1 -> GELU -> fc2 -> LayerScale
-// -> +res; ViT-g/14: LN -> w12 -> silu(gate) * value -> w3 instead, dtk_vit_model.ffn), output = residual stream after the last requested block (no final norm), CLS included.
+// -> +res; ViT-g/14: LN -> w12 -> silu(gate) * value -> w3 instead, dtk_vit_model.ffn), output = residual stream after the last requested block (no final norm), CLS included
+// (and, DINOv2 with registers, the dtk_vit_model.n_registers register rows between CLS and the patches: S = 1 + R + ph * pw).
 //
 // This file is the host side: the workspace plan, the kernel choice of a pass (GemmPath, launch_gemm / launch_gemm_split), the one
 // description of every GEMM role (run_gemm / run_gemm_split: vit_run and the stage API dtk_vit_gemm both go through it), vit_run, the ABI.
 //   vit_patch_embed.h   exact fp32 implicit GEMM on the f32-input MFMA (K = 3*14*14 = 588), mean/std fused in the load, or on the split-fp16 MFMA
 //   vit_rowwise.h       layernorm_kernel: one wave per token, fp32 statistics, 16-bit output; the row in NIT float4 per lane (D <= 1024: 4,
-//                       D <= 1536: 6); the final residual update, tap, CLS drop, range scan, zero fill
+//                       D <= 1536: 6); the final residual update, tap, prefix (CLS + registers) drop, range scan, zero fill
 //   gemm_tiled_kernel   (vit_gemm_tiled.h) C = A W^T on MFMA 16x16x32 (fp32 accumulate), 128x128 tiles, LDS double-buffered, with
 //                       fused epilogues: QKV split (Q pre-scaled by log2(e)/sqrt(d), V written transposed), GELU,
 //                       LayerScale + residual add into the fp32 stream.  The forms the blocks run on: vit_gemm_ws.h (K = 384,
@@ -45,6 +46,7 @@ namespace {
 // 30 -- fewer, longer launches: the attention's last partial round of workgroups weighs 0.7 % instead of 2.2 %, the
 // weight-stationary GEMMs load their weights a third as often; 301.4 -> 294.8 ms per step (profiles/r04_frame_batch_sweep.txt).
 constexpr int VIT_FRAME_BATCH = 90;
+constexpr int VIT_MAX_REGISTERS = 16;   // dtk_vit_model.n_registers (the hub's register models have 4)
 
 struct VitPlan {
     int S, Sp, FB;
@@ -57,7 +59,7 @@ inline bool vit_layer_split(const dtk_vit_layer& L) { return L.qkv_w_lo != nullp
 
 VitPlan vit_plan(const dtk_vit_model* m, int ph, int pw, int frames) {
     VitPlan p;
-    p.S = ph * pw + 1;
+    p.S = 1 + m->n_registers + ph * pw;   // CLS, the registers (DINOv2 with registers; 0 for the plain models), the patches
     p.Sp = (p.S + 127) / 128 * 128;
     const int fb = m->frame_batch > 0 ? m->frame_batch : VIT_FRAME_BATCH;
     p.FB = frames < fb ? frames : fb;
@@ -453,7 +455,7 @@ int vit_run(const dtk_vit_model* m, const float* frames, int nframes, int video_
             const long long t4 = rows * (D / 4);
             DTK_LAUNCH("vit_final_update", final_update_kernel<T>, dim3(dtk_cdiv(t4, 256)), dim3(256), 0, st, x, (const T*)delta,
                        tokens_out ? tokens_out + (size_t)f0 * S * D : (float*)nullptr,
-                       feat_out ? feat_out + (size_t)f0 * HW * D : (float*)nullptr, S, D, t4, ovf);
+                       feat_out ? feat_out + (size_t)f0 * HW * D : (float*)nullptr, S, D, t4, ovf, S - HW);
         } else {   // depth 0 (embedding + position encoding only) or a split last block: no pending update
             if (pending &&   // (qkv_out only: keep the residual-update check of the last block)
                 launch_layernorm<T>(x, delta, (const float*)nullptr, (const float*)nullptr, none, none, rows, D, m->ln_eps, ovf, st))
@@ -464,7 +466,7 @@ int vit_run(const dtk_vit_model* m, const float* frames, int nframes, int video_
             if (feat_out) {
                 const long long total4 = (long long)nf * HW * (D / 4);
                 DTK_LAUNCH("vit_drop_cls", drop_cls_kernel, dim3(dtk_cdiv(total4, 256)), dim3(256), 0, st, x,
-                           feat_out + (size_t)f0 * HW * D, S, D, total4);
+                           feat_out + (size_t)f0 * HW * D, S, D, total4, S - HW);
             }
         }
     }
@@ -531,7 +533,7 @@ template <typename F> int with_operand_type(bool bf16, F&& f) { return bf16 ? f(
 }  // namespace
 
 extern "C" size_t dtk_vit_workspace_bytes(const dtk_vit_model* m, int video_h, int video_w, int frames) {
-    if (!m || frames <= 0) return 0;
+    if (!m || frames <= 0 || m->n_registers < 0 || m->n_registers > VIT_MAX_REGISTERS) return 0;
     const int ph = 1 + (video_h - m->patch) / m->stride, pw = 1 + (video_w - m->patch) / m->stride;
     return vit_plan(m, ph, pw, frames).total;
 }
@@ -555,6 +557,9 @@ extern "C" int dtk_vit_forward(const dtk_vit_model* m, const float* frames, int 
         DTK_REQUIRE(m->ffn == DTK_VIT_FFN_GELU, "dtk_vit_forward: unknown ffn %d", m->ffn);
         DTK_REQUIRE(m->hidden == 0 || m->hidden == 4 * m->D, "dtk_vit_forward: a GELU MLP has hidden = 4 D (got %d)", m->hidden);
     }
+    DTK_REQUIRE(m->n_registers >= 0 && m->n_registers <= VIT_MAX_REGISTERS, "dtk_vit_forward: n_registers = %d: 0 .. %d register tokens",
+                m->n_registers, VIT_MAX_REGISTERS);
+    DTK_REQUIRE(m->n_registers == 0 || m->registers, "dtk_vit_forward: n_registers = %d but registers is a null pointer", m->n_registers);
     DTK_REQUIRE(video_h >= m->patch && video_w >= m->patch, "dtk_vit_forward: frame smaller than a patch");
     const int ph = 1 + (video_h - m->patch) / m->stride, pw = 1 + (video_w - m->patch) / m->stride;
     const VitPlan p = vit_plan(m, ph, pw, nframes);

@@ -10,9 +10,10 @@
 // m gives the same softmax as long as 2^(s - m) stays inside the range in which P keeps its precision: bf16 has fp32's exponent
 // range; fp16 ends at 65504 above and has full precision down to 2^-14 only.
 //   * The reference is ESTIMATED ONCE per query, before the key loop: the maximum of its scores against the first 64 keys (which
-//     hold the CLS token) and against the 32 keys of its own query tile (which hold its own key: the self score is the usual row
-//     maximum of a trained ViT).  That is a lower bound of the row maximum, hence p_max >= 1.  The kernels feed -m to the scores
-//     through the C operand of the first MFMA of a score block, so subtracting it costs no VALU work.
+//     hold the CLS token and, for DINOv2 with registers, the register tokens right behind it) and against the 32 keys of its own
+//     query tile (which hold its own key: the self score is the usual row maximum of a trained ViT; a trained register model's
+//     large-norm registers are among the first 64 keys).  That is a lower bound of the row maximum, hence p_max >= 1.  The
+//     kernels feed -m to the scores through the C operand of the first MFMA of a score block, so subtracting it costs no VALU work.
 //   * In the loop only a guard on the tile's row sum runs, one compare per tile: not (a lane's 32-key part < Operand::RESC_T),
 //     which also catches inf / NaN.  Nothing has overflowed yet while the part stays below Operand::POISON_T (fp16: RESC_T = 2^9,
 //     POISON_T = 2^15, so every p < 65504; bf16: 2^40 / 2^120).

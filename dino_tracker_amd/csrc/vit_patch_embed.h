@@ -7,7 +7,8 @@
 namespace {
 
 // ---------------------------------------------------------------------------------------------------------------
-// patch embedding: tokens[f][1 + r*pw + c][:] = W . patch(r,c) + b + pos[r*pw + c];  tokens[f][0] = cls_pos
+// patch embedding: tokens[f][1 + R + r*pw + c][:] = W . patch(r,c) + b + pos[r*pw + c];  tokens[f][0] = cls_pos;
+// tokens[f][1 .. R] = registers (DINOv2 with registers: no position encoding; R = 0 for the plain models), S = 1 + R + ph*pw
 // 32 patches x 32 output features per wave (MFMA 32x32x2 f32), 4 waves = 64 patches x 64 features per workgroup
 // ---------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void patch_embed_kernel(const float* __restrict__ frames, const float* __restrict__ Wp,
@@ -15,7 +16,7 @@ __global__ __launch_bounds__(256) void patch_embed_kernel(const float* __restric
                                                           const float* __restrict__ cls_pos,
                                                           const float* __restrict__ mean_std, float* __restrict__ x,
                                                           int H, int W, int ph, int pw, int D, int patch, int stride,
-                                                          int S) {
+                                                          int S, int R, const float* __restrict__ regs) {
     const int HW = ph * pw;
     const int K = 3 * patch * patch;
     const int frame = blockIdx.z;
@@ -45,10 +46,13 @@ __global__ __launch_bounds__(256) void patch_embed_kernel(const float* __restric
         for (int r = 0; r < 16; ++r) {
             const int i = (r & 3) + 8 * (r >> 2) + 4 * lk;
             const int pp = p0 + i;
-            if (pp < HW) x[((size_t)frame * S + 1 + pp) * D + co] = acc[r] + b + pos[(size_t)pp * D + co];
+            if (pp < HW) x[((size_t)frame * S + 1 + R + pp) * D + co] = acc[r] + b + pos[(size_t)pp * D + co];
         }
     }
-    if (blockIdx.x == 0 && (w >> 1) == 0 && lk == 0 && co < D) x[(size_t)frame * S * D + co] = cls_pos[co];
+    if (blockIdx.x == 0 && (w >> 1) == 0 && lk == 0 && co < D) {   // the prefix rows of this frame: once per feature
+        x[(size_t)frame * S * D + co] = cls_pos[co];
+        for (int r = 0; r < R; ++r) x[((size_t)frame * S + 1 + r) * D + co] = regs[(size_t)r * D + co];
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -104,7 +108,7 @@ __global__ __launch_bounds__(256) void patch_embed_split_kernel(const h4v* __res
                                                                 const float* __restrict__ bp, const float* __restrict__ pos,
                                                                 const float* __restrict__ cls_pos, float* __restrict__ x,
                                                                 int H, int W, int ph, int pw, int D, int S, int groups_x,
-                                                                int units, int slabs) {
+                                                                int units, int slabs, int R, const float* __restrict__ regs) {
     __shared__ h4v Xh[2 * PE_ROWPX], Xl[2 * PE_ROWPX];
     __shared__ __attribute__((aligned(16))) half_t Wsh[PE_NF * PE_WP], Wsl[PE_NF * PE_WP];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -172,19 +176,23 @@ __global__ __launch_bounds__(256) void patch_embed_split_kernel(const h4v* __res
             const int pc = pc0 + w * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
             if (pc < pw) {
                 const int pp = pr * pw + pc;
-                x[((size_t)frame * S + 1 + pp) * D + co] = acc[n][r] * (1.f / PE_WSCALE) + b + pos[(size_t)pp * D + co];
+                x[((size_t)frame * S + 1 + R + pp) * D + co] = acc[n][r] * (1.f / PE_WSCALE) + b + pos[(size_t)pp * D + co];
             }
         }
-        if (pr == 0 && pc0 == 0 && w == 0 && hh == 0) x[(size_t)frame * S * D + co] = cls_pos[co];
+        if (pr == 0 && pc0 == 0 && w == 0 && hh == 0) {   // the prefix rows of this frame: once per feature
+            x[(size_t)frame * S * D + co] = cls_pos[co];
+            for (int r = 0; r < R; ++r) x[((size_t)frame * S + 1 + r) * D + co] = regs[(size_t)r * D + co];
+        }
     }
 }
 
-// x [nf][S][D] = the tokens of `nf` frames.  The split-fp16 form runs for 14 x 14 patches at stride 7 when its inputs fit the two
+// x [nf][S][D] = the tokens of `nf` frames, S = 1 + n_registers + ph * pw.
+// The split-fp16 form runs for 14 x 14 patches at stride 7 when its inputs fit the two
 // scratch regions the caller lends (vit_run: `hid` and `delta`, both unused until the first block): the split planes of the
 // normalised frames go to `planes`, the split weights to `wsplit`.  Otherwise the generic kernel, which needs no scratch.
 inline int launch_patch_embed(const dtk_vit_model* m, const float* frames, int nf, int H, int W, int ph, int pw, float* x, void* planes,
                               size_t planes_bytes, void* wsplit, size_t wsplit_bytes, hipStream_t st) {
-    const int D = m->D, HW = ph * pw, S = HW + 1;
+    const int D = m->D, HW = ph * pw, R = m->n_registers, S = 1 + R + HW;
     const bool fits = (size_t)nf * H * W * 16 <= planes_bytes && (size_t)D * PE_K * 4 <= wsplit_bytes;
     if (m->patch == PE_P && m->stride == PE_S && fits) {
         h4v* fh = reinterpret_cast<h4v*>(planes);
@@ -199,10 +207,10 @@ inline int launch_patch_embed(const dtk_vit_model* m, const float* frames, int n
         const int groups_x = dtk_cdiv(pw, PE_TOK);
         const int units = groups_x * ph * nf, slabs = dtk_cdiv(D, PE_NF);
         DTK_LAUNCH("vit_patch_embed", patch_embed_split_kernel, dim3(8 * dtk_cdiv(units, 8) * slabs), dim3(256), 0, st, fh, fl, wh, wl,
-                   m->patch_b, m->pos, m->cls_pos, x, H, W, ph, pw, D, S, groups_x, units, slabs);
+                   m->patch_b, m->pos, m->cls_pos, x, H, W, ph, pw, D, S, groups_x, units, slabs, R, m->registers);
     } else {
         DTK_LAUNCH("vit_patch_embed", patch_embed_kernel, dim3(dtk_cdiv(HW, 64), dtk_cdiv(D, 64), nf), dim3(256), 0, st, frames,
-                   m->patch_w, m->patch_b, m->pos, m->cls_pos, m->mean_std, x, H, W, ph, pw, D, m->patch, m->stride, S);
+                   m->patch_w, m->patch_b, m->pos, m->cls_pos, m->mean_std, x, H, W, ph, pw, D, m->patch, m->stride, S, R, m->registers);
     }
     return DTK_OK;
 }

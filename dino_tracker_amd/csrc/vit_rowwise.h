@@ -124,12 +124,13 @@ __global__ __launch_bounds__(256) void zero_kernel(uint4* __restrict__ p, long l
 }
 
 // The LAST residual update of a pass, fused with what leaves the encoder (round 5): out = x + delta goes straight to tokens_out
-// [F][S][D] and / or feat_out [F][S-1][D] (CLS dropped); the fp32 stream x is dead after the last block and is not written back.
+// [F][S][D] and / or feat_out [F][S-P][D] (the P = 1 + n_registers prefix rows -- CLS and the registers -- dropped); the fp32 stream
+// x is dead after the last block and is not written back.
 // Replaces a statistics-free LayerNorm launch + a device copy / drop_cls pass: 2.8 GB of traffic instead of 5.0 per 90 frames.
 template <typename T>
 __global__ __launch_bounds__(256) void final_update_kernel(const float* __restrict__ x, const T* __restrict__ delta,
                                                            float* __restrict__ tokens_out, float* __restrict__ feat_out, int S, int D,
-                                                           long long total4, int* __restrict__ overflow) {
+                                                           long long total4, int* __restrict__ overflow, int P) {
     typedef typename Vec<T>::t4 T4;
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     bool sat = false;
@@ -144,7 +145,7 @@ __global__ __launch_bounds__(256) void final_update_kernel(const float* __restri
         sat = update_saturated<T>(d0, d1, d2, d3);   // (the check layernorm_kernel makes)
         v.x += d0; v.y += d1; v.z += d2; v.w += d3;
         if (tokens_out) reinterpret_cast<float4*>(tokens_out)[i] = v;
-        if (feat_out && s > 0) reinterpret_cast<float4*>(feat_out)[(f * (S - 1) + s - 1) * d4 + c] = v;
+        if (feat_out && s >= P) reinterpret_cast<float4*>(feat_out)[(f * (S - P) + s - P) * d4 + c] = v;
     }
     if (IsF16<T>::value && overflow && __any(sat) && (threadIdx.x & 63) == 0) atomicOr(overflow, 1);
 }
@@ -166,16 +167,16 @@ __global__ __launch_bounds__(256) void tap_kernel(const float* __restrict__ x, c
     reinterpret_cast<float4*>(out)[i] = o;
 }
 
-// fp32 tokens [F][S][D] (CLS first) -> token-major features [F][HW][D] (drop CLS)
+// fp32 tokens [F][S][D] (CLS first, then the registers) -> token-major features [F][HW][D] (drop the P = 1 + n_registers prefix rows)
 __global__ __launch_bounds__(256) void drop_cls_kernel(const float* __restrict__ x, float* __restrict__ out, int S, int D,
-                                                       long long total4) {
+                                                       long long total4, int P) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= total4) return;
     const int d4 = D / 4;
-    const long long row = i / d4;  // over F*(S-1)
+    const long long row = i / d4;  // over F*(S-P)
     const int c = (int)(i - row * d4);
-    const long long f = row / (S - 1), s = row - f * (S - 1);
-    reinterpret_cast<float4*>(out)[i] = reinterpret_cast<const float4*>(x)[(f * S + 1 + s) * d4 + c];
+    const long long f = row / (S - P), s = row - f * (S - P);
+    reinterpret_cast<float4*>(out)[i] = reinterpret_cast<const float4*>(x)[(f * S + P + s) * d4 + c];
 }
 
 // |x| >= 65504 or non-finite anywhere in a 16-bit tensor -> *flag |= bit (DTK_VIT_CHECK_RANGE: every intermediate tensor)

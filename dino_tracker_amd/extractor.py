@@ -7,6 +7,10 @@ weights are a plain state dict in upstream facebookresearch/dinov2 naming (`patc
   2. the file named by $DTK_DINOV2_WEIGHTS (e.g. the official dinov2_vits14_pretrain.pth),
   3. a seeded random initialisation if `random_seed=` is given (synthetic benchmarks / parity tests).
 Anything else raises: there is no silent fallback.
+Models: dinov2_vit{s,b,l,g}14 and their register variants dinov2_vit{s,b,l,g}14_reg (synth.VIT_CONFIGS).  A register model's state dict
+carries `register_tokens` [1, 4, D]: four rows between the CLS row and the patch rows, without position encoding (upstream
+prepare_tokens_with_masks), S = 1 + 4 + ph*pw.  `tokens`, `qkv`, the taps and the q / k / v facets return all S rows; `feat` (and with it
+get_dino_features_video) drops CLS and the registers.  Positions are `_fix_pos_enc`'s at every stride (docs/PARITY.md, "parity unpinned").
 Facets: `tokens` (block outputs, models/extractor.py:137-150) is the hot path.  The qkv hook output of a block
 (models/extractor.py:107-118) comes from the same device program (`qkv_out` of dtk_vit_forward: fp32 output of the
 16-bit-operand GEMM), so the key / query / value getters (:224-267) are reshapes of it like in the reference; the
@@ -87,7 +91,7 @@ class VitExtractor(nn.Module):
         self.gemm_wide_v1 = os.environ.get("DTK_VIT_GEMM_WIDE_V1", "0") == "1"   # the LDS-DMA GEMMs with round 5's direct-store epilogues (A / B; bit-identical)
         self.frame_batch = 0            # frames per pass of the encoder; 0 = the library's default
         if model_name not in VIT_CONFIGS:
-            raise NotImplementedError(f"{model_name}: the HIP encoder covers dinov2_vit{{s,b,l,g}}14 (d_head 64)")
+            raise NotImplementedError(f"{model_name}: the HIP encoder covers dinov2_vit{{s,b,l,g}}14 and dinov2_vit{{s,b,l,g}}14_reg (d_head 64)")
         self.model_name, self.stride, self.device = model_name, stride, device
         self.cfg = VIT_CONFIGS[model_name]
         if state_dict is None and os.environ.get("DTK_DINOV2_WEIGHTS"):
@@ -98,12 +102,27 @@ class VitExtractor(nn.Module):
             raise RuntimeError("no DINOv2 weights: pass state_dict=, set $DTK_DINOV2_WEIGHTS to a checkpoint in "
                                "upstream naming, or ask for random_seed= explicitly (torch.hub needs the network)")
         self.n_layers = self.get_n_layers()
+        # DINOv2 with registers (dinov2_vit*14_reg): `register_tokens` [1, R, D] sit between the CLS row and the patch rows.  The name and
+        # the state dict must agree -- a plain name would silently drop the registers of a register checkpoint, a _reg name without them
+        # would run a different network
+        self.n_registers = int(self.cfg.get("registers", 0))
+        reg = state_dict.get("register_tokens")
+        if self.n_registers:
+            if reg is None:
+                raise KeyError(f"{model_name}: the state dict has no 'register_tokens' (a DINOv2-with-registers checkpoint carries "
+                               f"register_tokens [1, {self.n_registers}, {self.cfg['dim']}])")
+            if tuple(reg.shape) != (1, self.n_registers, self.cfg["dim"]):
+                raise ValueError(f"{model_name}: 'register_tokens' has shape {tuple(reg.shape)}, expected "
+                                 f"(1, {self.n_registers}, {self.cfg['dim']})")
+        elif reg is not None:
+            raise ValueError(f"{model_name}: the state dict carries 'register_tokens' {tuple(reg.shape)}: it belongs to "
+                             f"{model_name}_reg; this model would drop the registers")
         self.swiglu = self.cfg.get("ffn") == "swiglu"   # ViT-g: mlp.w12 / mlp.w3 (upstream SwiGLUFFNFused) instead of mlp.fc1 / mlp.fc2
         # blocks present in the state dict (a truncated one serves the layers it has: tests need not build 40 blocks)
         self.n_blocks = sum(1 for i in range(self.n_layers) if f"blocks.{i}.norm1.weight" in state_dict)
         self.tiled_gemms = False  # run every GEMM on the tiled kernel (dtk_vit_model.flags; cross-check in the tests)
         self._sd = {k: v.detach().to(device=device, dtype=torch.float32).contiguous() for k, v in state_dict.items()
-                    if k.startswith(("cls_token", "pos_embed", "patch_embed.", "blocks."))}
+                    if k.startswith(("cls_token", "pos_embed", "register_tokens", "patch_embed.", "blocks."))}
         self._keep = []      # device tensors referenced by the C structs
         self._wcache = {}    # 16-bit weight tensors / split planes by (name, operand type[, "split"])
         self._layers_of = {}  # (operand type, split blocks) -> ctypes array of dtk_vit_layer (built on first need)
@@ -244,7 +263,8 @@ class VitExtractor(nn.Module):
     @torch.no_grad()
     def encode(self, frames: torch.Tensor, layer: Optional[int] = None, normalize: bool = True, want: str = "feat",
                defer_check: bool = False, taps: Optional[List[int]] = None):
-        """frames [n,3,H,W] fp32 -> `feat`: token-major [n, ph*pw, D] (CLS dropped) or `tokens`: [n, 1+ph*pw, D].
+        """frames [n,3,H,W] fp32 -> `feat`: token-major [n, ph*pw, D] (CLS and the registers dropped) or `tokens`: [n, 1+R+ph*pw, D]
+        (CLS, the R registers of a _reg model, the patches; `qkv` and `taps` have the same rows).
         normalize=True applies the ImageNet mean/std inside the patch-embedding kernel (utils.py:46,55).
         A saturated fp16 activation (see __init__) raises RuntimeError -- here, behind one stream synchronisation, or, with
         defer_check=True, in the caller's next `check_overflow()`: the call then returns with the kernels still in flight (what
@@ -263,7 +283,7 @@ class VitExtractor(nn.Module):
             self._overflow = torch.zeros(1, dtype=torch.int32, device=self.device)
         ms, overflow = self._ms[bool(normalize)], self._overflow
         D = self.cfg["dim"]
-        S = ph * pw + 1
+        S = 1 + self.n_registers + ph * pw
         if want not in ("tokens", "feat", "qkv", "taps"):
             raise ValueError(want)
         if want == "taps":   # the mean of the block outputs of `taps` in ONE pass (dtk_vit_model.tap_out); layer = the deepest of them
@@ -285,7 +305,8 @@ class VitExtractor(nn.Module):
                          self._sd["patch_embed.proj.bias"].data_ptr(), cls_pos.data_ptr(), pos.data_ptr(), ms.data_ptr(),
                          ctypes.cast(self._build_layers(operand_dtype, split_blocks), ctypes.POINTER(VitLayer)),
                          int(self.frame_batch), overflow.data_ptr(), None, 0, 0.0,
-                         VIT_FFN_SWIGLU if self.swiglu else 0, self.cfg["hidden"] if self.swiglu else 0)
+                         VIT_FFN_SWIGLU if self.swiglu else 0, self.cfg["hidden"] if self.swiglu else 0,
+                         self.n_registers, self._sd["register_tokens"].data_ptr() if self.n_registers else None)
             tap_out = None
             if want == "taps":
                 tap_out = torch.zeros((n, S, D), dtype=torch.float32, device=self.device)
@@ -420,7 +441,7 @@ class VitExtractor(nn.Module):
 
     def get_feature_from_input(self, input_img, layers: List[int]):  # models/extractor.py:137-150
         """input_img [B,3,H,W] ALREADY ImageNet-normalised (as the reference's caller does) -> mean over `layers` of
-        the block outputs, [B, 1+ph*pw, D]."""
+        the block outputs, [B, 1+R+ph*pw, D] (R = 4 register rows behind CLS for a _reg model, else 0)."""
         if len(set(layers)) == len(layers) and len(layers) > 1:
             # ONE pass up to the deepest requested block, the outputs of the requested blocks averaged on the way (round 6; rounds 1-5
             # re-ran blocks 0..l once per requested layer: O(L^2) for the reference's multi-layer mean)
@@ -449,7 +470,7 @@ class VitExtractor(nn.Module):
             return (self[i] for i in range(self._n))
 
     def get_qkv_feature_from_input(self, input_img):
-        """models/extractor.py:152-158: per layer, the output of blocks[l].attn.qkv, [B, 1+ph*pw, 3D]."""
+        """models/extractor.py:152-158: per layer, the output of blocks[l].attn.qkv, [B, 1+R+ph*pw, 3D]."""
         return VitExtractor._PerLayer(self.n_layers, lambda l: self.encode(input_img, layer=l, normalize=False, want="qkv"))
 
     def get_attn_feature_from_input(self, input_img):
@@ -512,7 +533,8 @@ class VitExtractor(nn.Module):
         return 1 + (h - self.get_patch_size()) // self.stride
 
     def get_patch_num(self, input_img_shape):
-        return 1 + self.get_height_patch_num(input_img_shape) * self.get_width_patch_num(input_img_shape)
+        """Rows of a token / qkv record: CLS, the registers of a _reg model, the patches (`_from_qkv` reshapes with it)."""
+        return 1 + self.n_registers + self.get_height_patch_num(input_img_shape) * self.get_width_patch_num(input_img_shape)
 
     def get_n_layers(self):
         return self.cfg["depth"]

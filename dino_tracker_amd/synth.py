@@ -111,6 +111,10 @@ VIT_CONFIGS = {  # models/extractor.py:183-222
     # upstream vit_giant2: ffn_layer="swiglufused", hidden = (int(4 * 1536 * 2 / 3) + 7) // 8 * 8 (mlp.w12 / mlp.w3 instead of fc1 / fc2)
     "dinov2_vitg14": dict(dim=1536, depth=40, heads=24, ffn="swiglu", hidden=4096),
 }
+# DINOv2 with registers (the hub's dinov2_vit*14_reg: num_register_tokens=4): the same widths, depths, heads and feed-forwards; four learned
+# rows between the CLS token and the patch tokens (state-dict key register_tokens [1, 4, D])
+VIT_CONFIGS.update({name + "_reg": dict(cfg, registers=4) for name, cfg in list(VIT_CONFIGS.items())})
+REGISTER_STD = 1.0   # make_vit_weights: per-element scale of the synthetic register tokens (a patch token of these weights is ~1.2)
 
 
 def make_vit_weights(model_name: str, seed: int = 2, pos_grid: int = 37, patch: int = 14,
@@ -119,7 +123,10 @@ def make_vit_weights(model_name: str, seed: int = 2, pos_grid: int = 37, patch: 
     `layerscale` is the mean of the LayerScale gammas: 1.0 is the hub models' init_values; with untrained attention
     (near-uniform averaging) that makes every token collapse onto a common vector, unlike trained DINOv2 features,
     so the benchmark uses a small value that keeps the residual stream dominated by the patch content.
-    `nblocks`: only the first blocks (the draws run block by block, so they equal the full model's)."""
+    `nblocks`: only the first blocks (the draws run block by block, so they equal the full model's).
+    A `_reg` name gets its sibling's values for every key plus `register_tokens` [1, 4, D], drawn from a generator of its own at the
+    scale of a patch token (REGISTER_STD: registers that are small next to the patches would not change the patch features by more
+    than the tests' tolerances, and a device that ignored them would pass; tests/test_vitreg_reference.py asserts the margin)."""
     cfg = VIT_CONFIGS[model_name]
     d, depth = cfg["dim"], cfg["depth"] if nblocks is None else min(int(nblocks), cfg["depth"])
     g = torch.Generator().manual_seed(seed)
@@ -156,6 +163,9 @@ def make_vit_weights(model_name: str, seed: int = 2, pos_grid: int = 37, patch: 
             sd[p + "mlp.fc2.weight"] = tn(d, 4 * d, std=0.03)
             sd[p + "mlp.fc2.bias"] = tn(d)
         sd[p + "ls2.gamma"] = layerscale * (1.0 + tn(d, std=0.1))
+    if cfg.get("registers"):
+        g_reg = torch.Generator().manual_seed(seed + 7919)
+        sd["register_tokens"] = torch.randn(1, cfg["registers"], d, generator=g_reg) * REGISTER_STD
     return sd
 
 

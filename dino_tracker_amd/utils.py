@@ -47,7 +47,7 @@ def get_dino_features_video_packed(video, model_name="dinov2_vitb14", facet="tok
     out = []
     for i in range(video.shape[0]):  # one frame at a time: the qkv record is 3x the token volume
         qkv = ex.encode(video[i:i + 1], layer=layer, normalize=True, want="qkv")
-        out.append(qkv[0, 1:, _FACET_ROW[facet] * d:(_FACET_ROW[facet] + 1) * d])
+        out.append(qkv[0, 1 + ex.n_registers:, _FACET_ROW[facet] * d:(_FACET_ROW[facet] + 1) * d])   # CLS and the registers dropped
     return torch.stack(out).contiguous()
 
 

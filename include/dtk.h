@@ -116,7 +116,7 @@ typedef struct dtk_vit_model {
                                    * SATURATE (FP16_OVFL mode) instead of becoming inf; a non-zero word means the features
                                    * are not trustworthy and the model should be run with DTK_VIT_BF16. */
     /* Round 6 -- the multi-layer form of get_feature_from_input (models/extractor.py:142-149: the MEAN over the requested layers of
-     * the block outputs) in ONE pass: after every block l with bit l of tap_mask set, tap_out [n][1 + ph*pw][D] += tap_scale x (the
+     * the block outputs) in ONE pass: after every block l with bit l of tap_mask set, tap_out [n][1 + R + ph*pw][D] += tap_scale x (the
      * residual stream after block l).  The caller zeroes tap_out and sets tap_scale = 1 / #layers.  NULL / 0: off. */
     float* tap_out;
     uint64_t tap_mask;
@@ -133,6 +133,13 @@ typedef struct dtk_vit_model {
      * tracks the fp16 range of what it stores as overflow bit 4.  DTK_VIT_GEMM_WS_V1 / GEMM_WIDE_V1 are refused for such a model. */
     int32_t ffn;
     int32_t hidden;               /* 0 = 4 D (GELU); 4096 for SwiGLU */
+    /* DINOv2 with registers (upstream prepare_tokens_with_masks, num_register_tokens = 4 for the hub's dinov2_vit*14_reg): R learned
+     * rows between the CLS row and the patch rows, inserted AFTER the position encoding is added (they carry none):
+     *     row 0 = cls_pos,  rows 1 .. R = registers[0 .. R-1],  rows 1 + R .. = patch tokens + pos,  S = 1 + R + ph*pw.
+     * They attend and are attended to like any token; feat_out drops them together with CLS.  0 (what a zero-initialised caller
+     * gets): the plain model.  0 <= n_registers <= 16. */
+    int32_t n_registers;
+    const float* registers;       /* DEVICE [n_registers][D] fp32 (register_tokens); NULL only with n_registers == 0 */
 } dtk_vit_model;
 #define DTK_VIT_FFN_GELU 0
 #define DTK_VIT_FFN_SWIGLU 1
@@ -156,9 +163,10 @@ typedef struct dtk_vit_model {
                                          * stand-alone stage; every other bit is refused */
 
 /* frames [n][3][video_h][video_w] fp32 in [0,1] -> block output of layer depth-1 (before the final norm):
- * tokens_out [n][1 + ph*pw][D] (CLS first; what get_feature_from_input returns) and/or
- * feat_out   [n][ph*pw][D]     (CLS dropped: the token-major feature volume of this library) and/or
- * qkv_out    [n][1 + ph*pw][3D] the output of blocks[depth-1].attn.qkv (the tensor the reference's qkv hook records,
+ * With R = n_registers (0 for the plain models):
+ * tokens_out [n][1 + R + ph*pw][D] (CLS first, then the registers, then the patches; what get_feature_from_input returns) and/or
+ * feat_out   [n][ph*pw][D]     (CLS and the registers dropped: the token-major feature volume of this library) and/or
+ * qkv_out    [n][1 + R + ph*pw][3D] the output of blocks[depth-1].attn.qkv (the tensor the reference's qkv hook records,
  *            models/extractor.py:107-118; the key / query / value facets are reshapes of it, :245-267).
  * Any of them may be NULL (not all). */
 size_t dtk_vit_workspace_bytes(const dtk_vit_model* m, int video_h, int video_w, int frames);
